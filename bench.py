@@ -16,9 +16,14 @@ Configs (BASELINE.json):
                  fp16 MFMA operands (--dtype bf16: bf16) / fp32 accumulation and master weights
 
 Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--config mnist|frey|fv|fvs|synth]
-                       [--scaling weak|strong]
+                       [--scaling weak|strong] [--dump-outputs DIR] [--full]
         (N > 1: torch.distributed.run, one process per GPU)
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, runs the W warmup and the K timed steps, writes the state the timed steps
+left (--dump-outputs) and prints the line.  --full adds the legs that take runs of their own:
+per-kernel device times and the roofline of the dominant launch, the CPU baseline
+(--no-cpu-baseline skips it) and, with N > 1, the strong-scaling leg (--no-strong skips it).
 """
 from __future__ import annotations
 
@@ -368,6 +373,38 @@ def timed_run(ctx, order, warmup, steps, dist, world=1, sync=False, warm_ms=0.0)
     return el, modes
 
 
+DUMP_BUDGET = 48 << 20   # bytes of all arrays of one --dump-outputs together
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array of `arrays` as path/<name>.npy (float32 or float64).  An array
+    beyond its share of DUMP_BUDGET is cut to a fixed sample of its elements (seed 0, ascending
+    flat indices), the same in every run of the same arguments."""
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_BUDGET // len(arrays)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if a.nbytes > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, cap // a.itemsize, replace=False))
+            a = a.ravel()[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def final_state(ctx, fv, elbo_sum, nsteps):
+    """What a caller of the timed path holds after its last step: the parameters, the Adagrad
+    state (full-variational: the (mu, sigma) posterior and its two Adagrad states) and the
+    SGVB/B sum over the timed steps.  The state getters are collectives at world > 1."""
+    out = {"params": ctx.get_params()}
+    if fv:
+        out.update(zip(("fv_mu", "fv_sigma", "fv_acc_mu", "fv_acc_sigma"), ctx.get_fv_state()))
+    else:
+        out["adagrad_state"] = ctx.get_adagrad_state()
+    out["elbo"] = np.array([elbo_sum / max(nsteps, 1), elbo_sum, nsteps], np.float64)   # mean, sum, steps
+    return out
+
+
 def comm_record(ctx, dist, world):
     """Per rank: the RCCL version, the overlap choice and the collective algorithm / protocol
     requested through the environment (RCCL picks per call when unset: "auto")."""
@@ -388,6 +425,12 @@ def main(argv=None):
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--batch", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what takes runs of its own: per-kernel device "
+                         "times and the roofline, the CPU baseline, with N > 1 the strong-scaling leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state the last timed step left (parameters, Adagrad state, SGVB/B sums) "
+                         "as DIR/<name>.npy; the inputs are the same in every run of the same arguments")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-strong", action="store_true", help="N > 1, weak scaling: skip the strong-scaling leg")
@@ -473,22 +516,12 @@ def main(argv=None):
                                 warm_ms=args.device_warm_ms)
     elbo_sum, nsteps = ctx.epoch_elbo()
     comm = comm_record(ctx, dist, world)
+    if args.dump_outputs:   # before anything else steps the model
+        state = final_state(ctx, fv, elbo_sum, nsteps)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, state)
 
-    # per-kernel device time (HIP events on the context's stream), after the timed region
-    prof = ctx.profile_steps(50 if not bf16 else 5)
     fl = phase_flops(D, H, Z, B, gaussian=gauss)
-    if fv:   # the (mu, sigma) updates stream 32 B per parameter (FVS: + the gradient read and
-        fl["fv_update"] = 32 * ctx.P   # the next step's sample written, Philox mode)
-        fl["fvs_update"] = 40 * ctx.P
-        fl["fvs_sample"] = 12 * ctx.P
-    dom = max((k for k in prof if k[0] in fl), key=lambda k: k[1])
-    traffic = committed_traffic(dom[0], PMC_FILES.get(args.config, ""))
-    if dom[0] in ("fv_update", "fvs_update", "fvs_sample"):   # HBM-bound streams (config 4)
-        achieved = fl[dom[0]] / (dom[1] * 1e-3) / 1e9
-        peak, bound, unit = PEAK_HBM_GBS, "hbm", "GB/s"
-    else:
-        achieved = fl[dom[0]] / (dom[1] * 1e-3) / 1e12
-        peak, bound, unit = (PEAK_BF16_TFLOPS if bf16 else PEAK_F32_TFLOPS), "mfma", "TFLOP/s"
     sflops = (fl["p1_enc_latent"] + fl["p4_decout_z"]) if C.get("estimator") == "FV" else \
         step_flops(D, H, Z, B, gaussian=gauss)
 
@@ -515,18 +548,33 @@ def main(argv=None):
         "graph": graph_modes,              # per rank: how the timed steps ran (vaeb_graph_status)
         "comm": comm,                      # per rank: RCCL version, overlap, algorithm / protocol
         "step_tflops": sflops / (el / steps) / 1e12,
-        "kernels_ms": {k: round(v, 5) for k, v in prof},
-        "roofline": {"bound": bound, "kernel": dom[0], "achieved": achieved, "peak": peak,
-                     "unit": unit, "frac": achieved / peak, "traffic": traffic,
-                     # traffic is not measured in this run: it is the committed rocprofv3 PMC pass
-                     # (FETCH_SIZE x 2 + WRITE_SIZE per launch, MI355X_MICROARCH.md) of this build
-                     "traffic_source": (os.path.relpath(PMC_FILES[args.config], ROOT)
-                                        if traffic is not None else None),
-                     ("bytes_per_launch" if bound == "hbm" else "flops_per_launch"): fl[dom[0]],
-                     "avg_launch_ms": dom[1]},
     }
+    if args.full:
+        # per-kernel device time (HIP events on the context's stream), after the timed region
+        prof = ctx.profile_steps(50 if not bf16 else 5)
+        if fv:   # the (mu, sigma) updates stream 32 B per parameter (FVS: + the gradient read and
+            fl["fv_update"] = 32 * ctx.P   # the next step's sample written, Philox mode)
+            fl["fvs_update"] = 40 * ctx.P
+            fl["fvs_sample"] = 12 * ctx.P
+        dom = max((k for k in prof if k[0] in fl), key=lambda k: k[1])
+        traffic = committed_traffic(dom[0], PMC_FILES.get(args.config, ""))
+        if dom[0] in ("fv_update", "fvs_update", "fvs_sample"):   # HBM-bound streams (config 4)
+            achieved = fl[dom[0]] / (dom[1] * 1e-3) / 1e9
+            peak, bound, unit = PEAK_HBM_GBS, "hbm", "GB/s"
+        else:
+            achieved = fl[dom[0]] / (dom[1] * 1e-3) / 1e12
+            peak, bound, unit = (PEAK_BF16_TFLOPS if bf16 else PEAK_F32_TFLOPS), "mfma", "TFLOP/s"
+        res["kernels_ms"] = {k: round(v, 5) for k, v in prof}
+        res["roofline"] = {"bound": bound, "kernel": dom[0], "achieved": achieved, "peak": peak,
+                           "unit": unit, "frac": achieved / peak, "traffic": traffic,
+                           # traffic is not measured in this run: it is the committed rocprofv3 PMC pass
+                           # (FETCH_SIZE x 2 + WRITE_SIZE per launch) of this build
+                           "traffic_source": (os.path.relpath(PMC_FILES[args.config], ROOT)
+                                              if traffic is not None else None),
+                           ("bytes_per_launch" if bound == "hbm" else "flops_per_launch"): fl[dom[0]],
+                           "avg_launch_ms": dom[1]}
     ctx.close()
-    if world > 1 and args.scaling == "weak" and not args.no_strong:
+    if args.full and world > 1 and args.scaling == "weak" and not args.no_strong:
         # the same run with one Bn-row global minibatch split over the ranks
         Bs, off_s, Bgs = row_split(Bn, world, rank, "strong")
         ctx2 = make_context(C, D, H, Z, Bs, Bgs, off_s, local, args, gauss, bf16, dist, rank, world)
@@ -537,7 +585,7 @@ def main(argv=None):
         ctx2.close()
         res["strong"] = {"value": Bgs * steps / el2, "ms_per_step": el2 / steps * 1e3, "global_batch": Bgs,
                          "rows_per_gpu": [row_split(Bn, world, r, "strong")[0] for r in range(world)]}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         if bf16:
             res["cpu_baseline"] = cpu_baseline(D, H, Z, B, x[:4 * B], budget_s=args.cpu_budget * 2, max_steps=8,
                                                single_kw={"max_steps": 1, "warm": 0})

@@ -2,14 +2,15 @@
 # interleaved rounds, after the fp32 GPU parity tests.  Usage: env_ab.sh VAR "v1 v2 ..." [bench args]
 set -o pipefail
 cd $GRAFT_REPO_ROOT
+OUT=${VAEB_OUT:-out}   # logs and result lines go here
 export TMPDIR=/tmp
 VAR=$1; VALS=$2; shift 2
-mkdir -p gpurun_out/envab
-timeout -k 10 400 python3 -u -m pytest tests/test_gpu_step.py tests/test_gpu_api.py -x -q --timeout 120 --timeout-method thread -m gpu > gpurun_out/envab/tests.log 2>&1 || { tail -30 gpurun_out/envab/tests.log; exit 1; }
-tail -2 gpurun_out/envab/tests.log
+mkdir -p $OUT/envab
+timeout -k 10 400 python3 -u -m pytest tests/test_gpu_step.py tests/test_gpu_api.py -x -q --timeout 120 --timeout-method thread -m gpu > $OUT/envab/tests.log 2>&1 || { tail -30 $OUT/envab/tests.log; exit 1; }
+tail -2 $OUT/envab/tests.log
 for r in 1 2 3; do
   for v in $VALS; do
-    env $VAR=$v timeout -k 10 120 python3 bench.py --steps 4000 --warmup 500 --no-cpu-baseline "$@" > gpurun_out/envab/v$v.json 2> gpurun_out/envab/v$v.err || { tail -5 gpurun_out/envab/v$v.err; exit 1; }
-    python3 -c "import json;d=json.load(open('gpurun_out/envab/v$v.json'));print('$VAR=$v', round(d['ms_per_step']*1000,2), 'us', {k: round(x*1000,2) for k,x in d['kernels_ms'].items()}, 'elbo', round(d['elbo'],4))"
+    env $VAR=$v timeout -k 10 120 python3 bench.py --full --steps 4000 --warmup 500 --no-cpu-baseline "$@" > $OUT/envab/v$v.json 2> $OUT/envab/v$v.err || { tail -5 $OUT/envab/v$v.err; exit 1; }
+    python3 -c "import json;d=json.load(open('$OUT/envab/v$v.json'));print('$VAR=$v', round(d['ms_per_step']*1000,2), 'us', {k: round(x*1000,2) for k,x in d['kernels_ms'].items()}, 'elbo', round(d['elbo'],4))"
   done
 done

@@ -28,7 +28,7 @@ for cfg in ${CONFIGS:-mnist frey fv fvs synth}; do
   cp $O/pmc_per_launch.json $OUT/profiles/pmc_${cfg}_per_launch.json
   cp $O/pmc_per_launch.json profiles/${ROUND:-r3}/pmc_${cfg}_per_launch.json
   [ $cfg = mnist ] && cp $O/trace/run_domain_stats.csv $OUT/profiles/domain_stats.csv
-  timeout -k 10 300 python3 bench.py --config $cfg > $O/bench_line.json 2> $O/bench_line.err || { tail $O/bench_line.err; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --config $cfg > $O/bench_line.json 2> $O/bench_line.err || { tail $O/bench_line.err; exit 1; }
   cp $O/bench_line.json $OUT/profiles/${pre}bench_line.json
   echo "== $cfg"; cut -c1-150 $O/trace/run_kernel_stats.csv | head -8
   python3 -c "

@@ -13,6 +13,6 @@ for cfg in fv fvs; do
   python3 scripts/pmc_summary.py $O/pmc_per_launch.json $O/fetch $O/write > $O/pmc_summary.txt || exit 1
   cp $O/trace/run_kernel_stats.csv $O/kernel_stats.csv
   cp $O/pmc_per_launch.json profiles/r1/pmc_${cfg}_per_launch.json
-  timeout -k 10 200 python3 bench.py --config $cfg > $O/bench_line.json 2> $O/bench_line.err || { tail $O/bench_line.err; exit 1; }
+  timeout -k 10 200 python3 bench.py --full --config $cfg > $O/bench_line.json 2> $O/bench_line.err || { tail $O/bench_line.err; exit 1; }
   echo "== $cfg"; cut -c1-150 $O/kernel_stats.csv | head -12; cut -c1-400 $O/bench_line.json
 done

@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 O=gpurun_out/prof_synth
 mkdir -p $O
-timeout -k 10 300 python3 bench.py --config synth > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
+timeout -k 10 300 python3 bench.py --full --config synth > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- python3 bench.py --config synth --steps 30 --warmup 3 --no-cpu-baseline > $O/bench_trace.json 2> $O/bench_trace.err || exit 1
 timeout -s KILL 200 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -o run -- python3 bench.py --config synth --steps 10 --warmup 2 --no-cpu-baseline > /dev/null 2> $O/fetch.err || exit 1
 timeout -s KILL 200 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write -o run -- python3 bench.py --config synth --steps 10 --warmup 2 --no-cpu-baseline > /dev/null 2> $O/write.err || exit 1

@@ -176,3 +176,109 @@ def test_bench_main_refuses_world_mismatch(monkeypatch):
     monkeypatch.setenv("WORLD_SIZE", "2")
     with pytest.raises(SystemExit):
         bench.main(["--gpus", "4"])
+
+
+def test_dump_outputs_writes_float_arrays_within_its_budget(tmp_path, monkeypatch):
+    """--dump-outputs: one .npy per array, float32 / float64; an array beyond its share of the
+    budget is cut to the same seeded sample of its elements in every run."""
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 3 * 400)
+    big = np.arange(1000, dtype=np.float32)
+    arrays = {"params": big, "small": np.arange(7, dtype=np.float32), "elbo": np.array([1, 2, 3], np.int64)}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in arrays}
+    assert sorted(os.listdir(tmp_path / "a")) == ["elbo.npy", "params.npy", "small.npy"]
+    assert a["params"].dtype == np.float32 and a["params"].size == 100
+    assert np.all(np.diff(a["params"]) > 0) and set(a["params"]) <= set(big)   # distinct elements, in order
+    assert np.array_equal(a["small"], arrays["small"])
+    assert a["elbo"].dtype == np.float64 and a["elbo"].tolist() == [1.0, 2.0, 3.0]
+    assert sum(v.nbytes for v in a.values()) <= 3 * 400
+    assert all(np.array_equal(a[n], np.load(tmp_path / "b" / f"{n}.npy")) for n in arrays)
+
+
+class _RecordingCtx:
+    """Stands in for the library context: records which legs bench.main runs."""
+    calls = []
+
+    def __init__(self, D, H, Z, B, **kw):
+        self.P, self.n, self.B = 12, 0, B
+
+    def set_data(self, x):
+        self.rows = x.shape[0]
+
+    def comm_count(self):
+        return 1
+
+    def set_params(self, p):
+        pass
+
+    def set_eps_mode(self, mode, seed=10):
+        pass
+
+    def busy(self, us):
+        pass
+
+    def update_many(self, order):
+        self.calls.append(("update_many", len(order)))
+        self.n += len(order)
+
+    def synchronize(self):
+        pass
+
+    def epoch_elbo(self):
+        n, self.n = self.n, 0
+        return -100.0 * n, n
+
+    def graph_status(self):
+        return "replay", ""
+
+    def comm_info(self):
+        return {"world": 1}
+
+    def get_params(self):
+        return np.full(self.P, 0.5, np.float32)
+
+    def get_adagrad_state(self):
+        return np.full(self.P, 2.0, np.float32)
+
+    def profile_steps(self, n):
+        self.calls.append(("profile_steps", n))
+        return [("p1_enc_latent", 0.012), ("p4_decout_z", 0.010)]
+
+    def close(self):
+        pass
+
+
+def _bench_line(monkeypatch, capsys, argv):
+    from vaeb_amd import _lib
+    _RecordingCtx.calls = []
+    monkeypatch.setattr(_lib, "Context", _RecordingCtx)
+    monkeypatch.setitem(bench.CONFIGS, "mnist", dict(bench.CONFIGS["mnist"], N=400))
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    bench.main(argv)
+    import json
+    return json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+
+
+def test_plain_run_times_its_steps_and_nothing_else(monkeypatch, capsys, tmp_path):
+    """A plain run: W warmup steps, exactly K timed steps in one call, the dump, the line; no
+    per-kernel profile, no roofline, no CPU baseline."""
+    line = _bench_line(monkeypatch, capsys, ["--gpus", "1", "--steps", "7", "--warmup", "3",
+                                             "--dump-outputs", str(tmp_path / "out")])
+    assert _RecordingCtx.calls == [("update_many", 1), ("update_many", 2), ("update_many", 7)]
+    assert line["steps"] == 7 and line["warmup"] == 3 and line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx(100 * 7 / (line["ms_per_step"] * 7 / 1e3), rel=1e-6)
+    assert line["unit"] == "images/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["metric"] == bench.CONFIGS["mnist"]["metric"] and line["elbo"] == -100.0
+    assert not {"kernels_ms", "roofline", "cpu_baseline", "strong"} & set(line)
+    assert sorted(os.listdir(tmp_path / "out")) == ["adagrad_state.npy", "elbo.npy", "params.npy"]
+    assert np.load(tmp_path / "out" / "elbo.npy").tolist() == [-100.0, -700.0, 7.0]
+    assert np.array_equal(np.load(tmp_path / "out" / "params.npy"), np.full(12, 0.5, np.float32))
+
+
+def test_full_run_adds_the_kernel_and_cpu_legs(monkeypatch, capsys):
+    line = _bench_line(monkeypatch, capsys, ["--steps", "5", "--warmup", "2", "--full", "--cpu-budget", "0.2"])
+    assert ("profile_steps", 50) in _RecordingCtx.calls and ("update_many", 5) in _RecordingCtx.calls
+    assert line["kernels_ms"] == {"p1_enc_latent": 0.012, "p4_decout_z": 0.01}
+    assert line["roofline"]["kernel"] == "p1_enc_latent" and line["roofline"]["bound"] == "mfma"
+    assert line["cpu_baseline"]["value"] > 0 and line["steps"] == 5

@@ -89,7 +89,7 @@ def _rank(rank, world, port, q, fail_rank=None):
     buf = io.StringIO()
     try:
         with redirect_stdout(buf):
-            bench.main(["--gpus", str(world), "--steps", "40", "--warmup", "4", "--no-cpu-baseline"])
+            bench.main(["--gpus", str(world), "--steps", "40", "--warmup", "4", "--full", "--no-cpu-baseline"])
     except SystemExit as e:
         q.put((rank, "exit", str(e.code)))
         raise

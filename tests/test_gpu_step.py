@@ -469,7 +469,7 @@ def test_atomic_and_slab_handoffs_agree(kw, monkeypatch):
 
 @pytest.mark.parametrize("kw", [dict(D=784, H=500, Z=20), dict(D=560, H=200, Z=2, continuous=True)],
                          ids=["mnist20", "frey2"])
-def test_deferred_dw2_is_bitwise_the_same_step(kw, monkeypatch):
+def test_deferred_dw2_is_bitwise_the_same_step(kw, monkeypatch, tmp_path):
     """The deferred dW2 (step t's dW2 | dW6 + Adagrad in step t+1's encoder launch, the last
     one flushed when the host reads the state) runs the same tiles with the same K split as
     the in-step form (VAEB_DW2_DEFER=0): parameters, Adagrad state and ELBO bit for bit, with
@@ -494,7 +494,7 @@ def test_deferred_dw2_is_bitwise_the_same_step(kw, monkeypatch):
             out.append(ctx.update(6))                          # sync step with a pending dW2
             out.append(ctx.validate(x[:200]))                  # flush inside the evaluation
             ctx.update_many(np.array([0, 7, 2], np.int32))
-            ckpt = f"/tmp/vaeb_dw2_{defer}_{int(use_graph)}.ckpt"
+            ckpt = str(tmp_path / f"vaeb_dw2_{defer}_{int(use_graph)}.ckpt")
             ctx.checkpoint_save(ckpt)
             ctx.update_many(np.array([5, 5], np.int32))
             out.append(ctx.get_params())

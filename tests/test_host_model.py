@@ -1,7 +1,9 @@
 """Host-side pieces of the drop-in that run without a GPU: parameter layout and init
 (restated in vaeb_amd/model.py, must equal the oracle), the static checkpoint reader
-(vaeb_amd/pickle_static.py) on files written by vaeb_amd's own writer and -- where the
-reference snapshot is present -- on the reference's .mdl / modelFrey.pkl files."""
+(vaeb_amd/pickle_static.py) on files written by vaeb_amd's own writer and on the reference's
+.mdl / modelFrey.pkl files (tests/golden/ref_*.gz: the reference's own pickle streams, byte
+for byte except that every weight string is zero-filled so that they compress)."""
+import gzip
 import os
 import pickle
 
@@ -11,7 +13,14 @@ import pytest
 from oracle import vaeb_oracle as O
 from vaeb_amd import model, pickle_static
 
-REF = "/root/reference"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def _unpacked(tmp_path, name):
+    out = tmp_path / name
+    with gzip.open(os.path.join(GOLDEN, name + ".gz"), "rb") as fh:
+        out.write_bytes(fh.read())
+    return str(out)
 
 
 @pytest.mark.parametrize("continuous", [False, True])
@@ -47,13 +56,12 @@ def test_static_reader_never_imports(tmp_path):
     assert isinstance(obj, pickle_static.Reduce) and obj.func == ("os", "system")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference snapshot not present")
-def test_reads_reference_checkpoints():
-    hdr, p = pickle_static.read_mdl(os.path.join(REF, "reconstruction_res/VAE_continuous_2.mdl"))
+def test_reads_reference_checkpoints(tmp_path):
+    hdr, p = pickle_static.read_mdl(_unpacked(tmp_path, "ref_VAE_continuous_2.mdl"))
     assert hdr["n_hidden_units"] == 200 and len(p) == 12 and p[0].shape == (560, 200)
-    hdr8, p8 = pickle_static.read_mdl(os.path.join(REF, "full_vb_res/continuous_2.mdl"))
+    hdr8, p8 = pickle_static.read_mdl(_unpacked(tmp_path, "ref_fullvb_continuous_2.mdl"))
     assert "genericEstimator" not in hdr8  # the 8-field header of the current VAEB.save
-    frey = pickle_static.read_array_pickle(os.path.join(REF, "modelFrey.pkl"))
+    frey = pickle_static.read_array_pickle(_unpacked(tmp_path, "ref_modelFrey.pkl"))
     assert [a.shape for a in frey][:2] == [(560, 200), (200, 2)]
 
 
