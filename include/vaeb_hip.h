@@ -139,6 +139,27 @@ int vaeb_reconstruct_full(vaeb_ctx* ctx, const float* x, int64_t n, int32_t n_sa
  * :237-245): z [n x Z] -> mean [n x D] (sigmoid(tanh(z W1 + b1) W2 + b2)) and, for the Gaussian
  * decoder, the log-sigma head [n x D] (out_lv; NULL to skip).  fp32 contexts. */
 int vaeb_decode(vaeb_ctx* ctx, const float* z, int64_t n, float* out_mu, float* out_lv);
+/* Encoder outputs for host x [n x D]: mu and log-variance [n x Z] (VAEB.py:245-251).
+ * Either output may be NULL.  fp32 contexts. */
+int vaeb_encode(vaeb_ctx* ctx, const float* x, int64_t n, float* out_mu, float* out_lv);
+
+/* Extension (no reference counterpart): the K-sample importance-weighted estimate of
+ * sum_i log p(x_i), with the encoder as the proposal:
+ *   z_k = mu(x) + exp(lv(x) / 2) eps_k,  log w_k = log p(x | z_k) + 1/2 sum_j (eps_kj^2 + lv_j - z_kj^2),
+ *   IW_K(x) = logsumexp_k log w_k - log K    (IW_1: the one-sample LA estimate; rises to log p(x) with K).
+ * out_sum: the sum over the n rows (double).  out_rows: per-row IW_K [n], or NULL.
+ * Noise: Philox validation streams 1..K keyed by global row, exactly the streams
+ * vaeb_reconstruct_sampled uses.  In host eps mode, rows [k*n, (k+1)*n) of the pushed
+ * eps, which must hold n*K rows.  1 <= K <= 2^20.  The data term only (no thetaPrior), at the
+ * current theta (VAEB_EST_FVS: the posterior mean); the context's L, estimator and objective
+ * do not enter.  A non-finite log w makes that row's value and the sum NaN.  Changes no
+ * training state.  fp32 contexts. */
+int vaeb_marginal_ll(vaeb_ctx* ctx, const float* x, int64_t n, int32_t K,
+                     double* out_sum, float* out_rows);
+/* The same over the resident validation set (vaeb_set_valid_data): this rank's share of
+ * the rows, all-reduced over the communicator like vaeb_validate_resident (host eps mode:
+ * eps for nval*K rows, sample-major, global row order). */
+int vaeb_marginal_ll_resident(vaeb_ctx* ctx, int32_t K, double* out_sum);
 
 /* Data parallel (one ctx per rank): the library owns an RCCL communicator; the 128-byte
  * unique id is produced on rank 0 and broadcast by the host (e.g. torch.distributed). */

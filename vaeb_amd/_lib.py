@@ -31,7 +31,7 @@ EXPORTS = [
     "vaeb_get_adagrad_state", "vaeb_set_fv_state", "vaeb_get_fv_state", "vaeb_set_eps_mode",
     "vaeb_push_eps", "vaeb_set_step", "vaeb_get_step", "vaeb_update", "vaeb_update_async", "vaeb_update_many",
     "vaeb_epoch_elbo", "vaeb_synchronize", "vaeb_validate", "vaeb_reconstruct", "vaeb_reconstruct_sampled",
-    "vaeb_reconstruct_full", "vaeb_decode",
+    "vaeb_reconstruct_full", "vaeb_decode", "vaeb_encode", "vaeb_marginal_ll", "vaeb_marginal_ll_resident",
     "vaeb_comm_unique_id", "vaeb_comm_init", "vaeb_comm_count", "vaeb_set_valid_data", "vaeb_validate_resident",
     "vaeb_checkpoint_save", "vaeb_checkpoint_load", "vaeb_get_grads", "vaeb_get_activation", "vaeb_push_fv_noise",
     "vaeb_ae_create", "vaeb_ae_destroy", "vaeb_ae_num_params", "vaeb_ae_set_data", "vaeb_ae_set_params",
@@ -123,6 +123,9 @@ def load():
         "vaeb_reconstruct_sampled": ([_P, _F, _I64, ctypes.c_int32, _F], ctypes.c_int),
         "vaeb_reconstruct_full": ([_P, _F, _I64, ctypes.c_int32, _F, _F], ctypes.c_int),
         "vaeb_decode": ([_P, _F, _I64, _F, _F], ctypes.c_int),
+        "vaeb_encode": ([_P, _F, _I64, _F, _F], ctypes.c_int),
+        "vaeb_marginal_ll": ([_P, _F, _I64, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), _F], ctypes.c_int),
+        "vaeb_marginal_ll_resident": ([_P, ctypes.c_int32, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
         "vaeb_comm_unique_id": ([ctypes.POINTER(ctypes.c_uint8)], ctypes.c_int),
         "vaeb_comm_init": ([_P, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int32, ctypes.c_int32], ctypes.c_int),
         "vaeb_get_grads": ([_P, _F, _I64], ctypes.c_int),
@@ -382,6 +385,31 @@ class Context:
         lv = np.empty_like(mu) if (log_sigma and self.cfg.decoder == DEC_GAUSSIAN) else None
         check(self.lib.vaeb_decode(self.h, fptr(z), z.shape[0], fptr(mu), fptr(lv) if lv is not None else None))
         return mu, lv
+
+    def encode(self, x, mu=True, log_var=True):
+        """(mu, log_var) of the encoder at x [n x D] (VAEB.py:245-251), each [n x Z]; an output
+        not asked for is None."""
+        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
+        m = np.empty((x.shape[0], self.cfg.Z), np.float32) if mu else None
+        v = np.empty((x.shape[0], self.cfg.Z), np.float32) if log_var else None
+        check(self.lib.vaeb_encode(self.h, fptr(x), x.shape[0], fptr(m) if mu else None, fptr(v) if log_var else None))
+        return m, v
+
+    def marginal_ll(self, x, K, rows=False):
+        """K-sample importance-weighted estimate of sum_i log p(x_i) (vaeb_marginal_ll); with
+        rows=True also the per-row values: (sum, [n])."""
+        x = np.ascontiguousarray(x, np.float32)
+        out = ctypes.c_double()
+        r = np.empty(x.shape[0], np.float32) if rows else None
+        check(self.lib.vaeb_marginal_ll(self.h, fptr(x), x.shape[0], int(K), ctypes.byref(out),
+                                        fptr(r) if rows else None))
+        return (out.value, r) if rows else out.value
+
+    def marginal_ll_resident(self, K):
+        """The same sum over the resident validation set (this rank's share, all-reduced)."""
+        out = ctypes.c_double()
+        check(self.lib.vaeb_marginal_ll_resident(self.h, int(K), ctypes.byref(out)))
+        return out.value
 
     def time_update_many(self, indices):
         """(GPU ms, host enqueue ms) of one update_many call (diagnostics)."""

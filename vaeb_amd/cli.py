@@ -5,7 +5,7 @@ Same `command_line_args` / `command_line_flags` dicts (including the misspelt
 `full_varational`), the same `--name value` / `--flag` parsing with a warning (not an
 error) for unused arguments, the same stdout lines and trace CSV.  Keys ADDED (never
 renamed): device, rng, objective, max_eval_rows, trace_dedup, fv_sample, state_file,
-resume_file, world_size, dp_scaling, dtype (args) and synthetic (flag).
+resume_file, world_size, dp_scaling, dtype, iw_samples (args) and synthetic (flag).
 
 Data parallelism: `--world_size N` runs N ranks, one process per GPU.
 Without a launcher the CLI starts them itself (`python -m vaeb_amd ...` per rank, RANK /
@@ -91,6 +91,10 @@ def parse_args(argv=None, spec=None, flags=None, flag_prefix='--', out=print):
         arg_dict[arg_name] = get_arg(arg_name, args, default, type_)
     for flag_name in (flags or command_line_flags):
         arg_dict[flag_name] = get_flag(flag_name, args, flag_prefix)
+    if spec is None:
+        # added by vaeb_amd: K > 0 prints the K-sample importance-weighted marginal
+        # log-likelihood of the validation set after the last epoch (train_model)
+        arg_dict['iw_samples'] = get_arg('iw_samples', args, 0, int)
     if len(args) > 0 and spec is None:
         out('Have unused args: {0}'.format(args))
     return arg_dict
@@ -101,6 +105,8 @@ def print_args(args, out=print):
     out('Parameters used:')
     out('--------------------------------------')
     for k, v in args.items():
+        if k == 'iw_samples' and not v:
+            continue   # off: the listing stays the one of a run without the argument
         out('\t{0}: {1}'.format(k, v))
     out('--------------------------------------')
 
@@ -244,6 +250,11 @@ def train_model(args):
         if trace and not dedup:  # the reference writes every row twice (VAEB.py:591-593)
             with open(trace_file, 'a') as f:
                 f.write('{0},{1},{2}\n'.format(model.N * (epoch + 1), LB, LBvalidation))
+    iw_samples = int(args.get('iw_samples', 0) or 0)
+    if iw_samples > 0:
+        # every rank joins (the resident rows are sharded and the sum all-reduced); rank 0 prints
+        ml = model.marginal_likelihood_resident(iw_samples) / x_valid.shape[0]
+        say("          [Marginal log-likelihood on validation set (K=%s): %s]" % (iw_samples, ml))
     if len(save_file) > 0 and lead:
         model.save(save_file)
     if args.get('state_file'):

@@ -24,6 +24,7 @@
 #include "hfuse.hpp"
 #include "latent.hpp"
 #include "latent_bwd.hpp"
+#include "iwae.hpp"
 #include "h16_engines.hpp"
 #include "ae_mlp.hpp"
 
@@ -140,6 +141,8 @@ struct vaeb_ctx {
           *y = nullptr, *dA2 = nullptr, *dA6 = nullptr, *dA1 = nullptr, *dZ = nullptr,
           *dMuLv = nullptr, *dA3 = nullptr, *kl_part = nullptr, *lp_part = nullptr;
     float* yacc = nullptr;        // sampled reconstruction sum (allocated on first use)
+    float* iw = nullptr;          // vaeb_marginal_ll scratch (allocated on first use): latent terms
+                                  // [cap * L], running (max, sum) [cap][2], row values [cap]
     float *slab_ml = nullptr, *slab_dz = nullptr;  // folded-latent partial slabs (latent.hpp)
     int *cnt_ml = nullptr, *cnt_dz = nullptr;      // their per-row-block arrival counters
     uint64_t *acc_ml = nullptr, *acc_dz = nullptr; // atomic hand-off accumulators (zeroed)
@@ -1326,7 +1329,7 @@ const char* vaeb_last_error(void) { return g_err.c_str(); }
 
 int vaeb_version(int32_t* major, int32_t* minor) {
     if (major) *major = 0;
-    if (minor) *minor = 1;
+    if (minor) *minor = 2;
     return 0;
 }
 
@@ -1478,7 +1481,7 @@ int vaeb_destroy(vaeb_ctx* c) {
     float* fp[] = {c->theta2[0], c->theta2[1], c->acc, c->grad, c->fvmu, c->fvsg, c->fvam, c->fvas, c->fv_part, c->data, c->xeval, c->xval,
                    c->eps_in, c->h, c->mu, c->lv, c->eps, c->z, c->hd, c->y, c->dA2, c->dA1,   // dA6 lives in dA2's block
                    c->dZ, c->dMuLv, c->dA3, c->kl_part, c->lp_part, c->slab_ml, c->slab_dz, c->yacc,
-                   c->fvzeta};
+                   c->fvzeta, c->iw};
     for (float* p : fp) if (p) hipFree(p);
     if (c->cnt_ml) hipFree(c->cnt_ml);
     if (c->cnt_dz) hipFree(c->cnt_dz);
@@ -1794,6 +1797,19 @@ static int eval_chunk_f32(vaeb_ctx* c, int epar, const float* x, int rows, int64
     return 0;
 }
 
+// eval_acc[0] on the host, after an optional all-reduce of it over the ranks: the call's
+// one stream synchronisation.
+static int eval_acc_read(vaeb_ctx* c, bool allreduce, double* out) {
+    if (allreduce && c->comm) {
+        ncclResult_t r = ncclAllReduce(c->eval_acc, c->eval_acc, 1, ncclDouble, ncclSum, c->comm, c->s);
+        if (r != ncclSuccess) return fail(VAEB_ERR_COMM, "ncclAllReduce(validation): %s", ncclGetErrorString(r));
+    }
+    HIP_TRY(hipMemcpyAsync(c->h_d2, c->eval_acc, 2 * sizeof(double), hipMemcpyDeviceToHost, c->s));
+    HIP_TRY(hipStreamSynchronize(c->s));
+    *out = c->h_d2[0];
+    return 0;
+}
+
 // SGVB of n evaluated rows from eval_acc (after an optional all-reduce of it over the
 // ranks); the FV estimators add thetaPrior: x.shape[0] * (sum logp + sum KL) + thetaPrior
 // (VAEB.py:364).
@@ -1810,13 +1826,8 @@ static int eval_finish(vaeb_ctx* c, int64_t n, bool allreduce, double* out_sum) 
         HIP_TRY(hipStreamSynchronize(c->s));
         for (float p : parts) tp += p;
     }
-    if (allreduce && c->comm) {
-        ncclResult_t r = ncclAllReduce(c->eval_acc, c->eval_acc, 1, ncclDouble, ncclSum, c->comm, c->s);
-        if (r != ncclSuccess) return fail(VAEB_ERR_COMM, "ncclAllReduce(validation): %s", ncclGetErrorString(r));
-    }
-    HIP_TRY(hipMemcpyAsync(c->h_d2, c->eval_acc, 2 * sizeof(double), hipMemcpyDeviceToHost, c->s));
-    HIP_TRY(hipStreamSynchronize(c->s));
-    const double data = c->h_d2[0];
+    double data = 0.0;
+    if (int rc = eval_acc_read(c, allreduce, &data)) return rc;
     *out_sum = fvx ? (double)n * data + tp : data;
     return 0;
 }
@@ -2119,6 +2130,139 @@ int vaeb_decode(vaeb_ctx* c, const float* z, int64_t n, float* out_mu, float* ou
     }
     HIP_TRY(hipStreamSynchronize(c->s));
     return 0;
+}
+
+// ------------------------------------------------------------------ encoder outputs, IWAE bound
+// The encoder and heads of one fp32 chunk (rows at x = global rows [r0, r0 + rows)): c->mu and
+// c->lv hold it afterwards (VAEB.py:245-251).  The forward's own launches with zero noise and
+// one plane; what they also write (eps, z, hd plane 0, the KL partials) is scratch here.
+static int encode_chunk_f32(vaeb_ctx* c, int epar, const float* x, int rows, int64_t r0, StepArgs* out) {
+    StepArgs a = make_args(c, epar, rows, MODE_EVAL, x, false);
+    a.L = 1; a.Me = a.Mbp;
+    a.est = EST_LB;
+    a.eps_mode = 2;
+    a.row_base_add = r0;
+    launch_bigk<1>(c->s, PEnc{a, nullptr, a.Mbp, a.H, a.D});
+    CHECK_LAUNCH();
+    if (fused_latent(c)) {
+        if (a.Z <= 16) hipLaunchKernelGGL(heads_dechid_kernel<1>, dim3(a.Mbp / 16), dim3(512), 0, c->s, a);
+        else hipLaunchKernelGGL(heads_dechid_kernel<2>, dim3(a.Mbp / 16), dim3(512), 0, c->s, a);
+    } else {
+        launch_tile<1, 1, 4, 2, 8>(c->s, PHeads{a, a.Mbp, a.Z, a.H});
+    }
+    CHECK_LAUNCH();
+    if (out) *out = a;
+    return 0;
+}
+
+int vaeb_encode(vaeb_ctx* c, const float* x, int64_t n, float* out_mu, float* out_lv) {
+    if (!c || !x || n <= 0) return fail(VAEB_ERR_ARG, "bad arguments");
+    if (is_bf16(c)) return fail(VAEB_ERR_ARG, "vaeb_encode is served by fp32 contexts");
+    const vaeb_config& g = c->c;
+    const int chunk = g.max_eval_rows;
+    int epar = c->par;
+    if (int rc = eval_arena(c, &epar)) return rc;
+    for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+        const int rows = (int)std::min<int64_t>(chunk, n - r0);
+        HIP_TRY(hipMemcpyAsync(c->xeval, x + r0 * g.D, sizeof(float) * (size_t)rows * g.D, hipMemcpyHostToDevice, c->s));
+        if (int rc = encode_chunk_f32(c, epar, c->xeval, rows, r0, nullptr)) return rc;
+        const size_t nb = sizeof(float) * (size_t)rows * g.Z;
+        if (out_mu) HIP_TRY(hipMemcpyAsync(out_mu + r0 * g.Z, c->mu, nb, hipMemcpyDeviceToHost, c->s));
+        if (out_lv) HIP_TRY(hipMemcpyAsync(out_lv + r0 * g.Z, c->lv, nb, hipMemcpyDeviceToHost, c->s));
+    }
+    HIP_TRY(hipStreamSynchronize(c->s));
+    return 0;
+}
+
+// IW_K of one chunk (iwae.hpp): `rows` device rows at x = global rows [r0, r0 + rows); eps_k0:
+// host eps mode, sample 0's noise row of the chunk's row 0 (sample k is eps_ld rows further).
+// Adds the chunk's sum to eval_acc[0]; the row values go to out_rows (host) when given.
+static int iw_chunk_f32(vaeb_ctx* c, int epar, const float* x, int rows, int64_t r0, int K, const float* eps_k0,
+                        int64_t eps_ld, float* out_rows) {
+    const vaeb_config& g = c->c;
+    StepArgs a;
+    if (int rc = encode_chunk_f32(c, epar, x, rows, r0, &a)) return rc;
+    const int64_t planes = (int64_t)c->cap * g.L;   // rows of z / hd / lp_part
+    IwArgs w{};
+    w.Z = g.Z; w.Mb = rows; w.Mbp = a.Mbp; w.nctD = a.nctD;
+    w.K = K; w.logK = (float)std::log((double)K);
+    w.row0 = r0;
+    w.eps_mode = c->eps_mode == VAEB_EPS_HOST ? 1 : 0;
+    w.seed = c->seed; w.step = c->step;
+    w.eps_in = eps_k0; w.eps_ld = eps_ld;
+    w.mu = c->mu; w.lv = c->lv; w.z = c->z; w.lp_part = c->lp_part;
+    w.lat = c->iw; w.ms = c->iw + planes; w.rows = w.ms + 2 * (int64_t)c->cap;
+    const int smax = (int)std::min<int64_t>(planes / a.Mbp, K);
+    for (int k0 = 0; k0 < K; k0 += smax) {
+        const int S = std::min(smax, K - k0);
+        w.k0 = k0; w.S = S;
+        hipLaunchKernelGGL(iw_sample_kernel, dim3((unsigned)(S * (a.Mbp / 16))), dim3(256), 0, c->s, w);
+        CHECK_LAUNCH();
+        StepArgs d = a;
+        d.L = S; d.Me = S * a.Mbp;
+        launch_tile<1, 4, 1, 1, 8>(c->s, PDecHid{d, d.Me, d.H, d.Z});
+        CHECK_LAUNCH();
+        if (gaussian(c)) launch_bigk<2>(c->s, PDecOut{d, nullptr, d.Me, d.D, d.H});
+        else launch_bigk<1>(c->s, PDecOut{d, nullptr, d.Me, d.D, d.H});
+        CHECK_LAUNCH();
+        hipLaunchKernelGGL(iw_lse_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, c->s, w);
+        CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(iw_sum_kernel, dim3(1), dim3(256), 0, c->s, w.rows, (int64_t)rows, c->eval_acc);
+    CHECK_LAUNCH();
+    if (out_rows) HIP_TRY(hipMemcpyAsync(out_rows, w.rows, sizeof(float) * (size_t)rows, hipMemcpyDeviceToHost, c->s));
+    return 0;
+}
+
+// Argument / state checks shared by the two marginal-likelihood calls, and the lazily
+// allocated scratch; n: the rows the pushed eps must cover K times.
+static int iw_begin(vaeb_ctx* c, int64_t n, int32_t K, int* epar) {
+    if (is_bf16(c)) return fail(VAEB_ERR_ARG, "vaeb_marginal_ll is served by fp32 contexts");
+    if (K < 1 || K > (1 << 20))
+        return fail(VAEB_ERR_ARG, "K = %d: 1 to 2^20 samples (the Philox sample-stream field)", K);
+    if (c->eps_mode == VAEB_EPS_HOST && c->eps_rows != n * K)
+        return fail(VAEB_ERR_STATE, "host eps mode: the marginal likelihood needs eps for %lld rows (n * K), pushed %lld",
+                    (long long)(n * K), (long long)c->eps_rows);
+    if (!c->iw) {
+        if (int rc = dalloc(&c->iw, (size_t)c->cap * (c->c.L + 3))) return rc;
+    }
+    HIP_TRY(hipMemsetAsync(c->eval_acc, 0, 2 * sizeof(double), c->s));
+    return eval_arena(c, epar);
+}
+
+int vaeb_marginal_ll(vaeb_ctx* c, const float* x, int64_t n, int32_t K, double* out_sum, float* out_rows) {
+    if (!c || !x || n <= 0 || !out_sum) return fail(VAEB_ERR_ARG, "bad arguments");
+    int epar = 0;
+    if (int rc = iw_begin(c, n, K, &epar)) return rc;
+    const vaeb_config& g = c->c;
+    const int chunk = g.max_eval_rows;
+    for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+        const int rows = (int)std::min<int64_t>(chunk, n - r0);
+        HIP_TRY(hipMemcpyAsync(c->xeval, x + r0 * g.D, sizeof(float) * (size_t)rows * g.D, hipMemcpyHostToDevice, c->s));
+        if (int rc = iw_chunk_f32(c, epar, c->xeval, rows, r0, K, c->eps_in ? c->eps_in + r0 * g.Z : nullptr, n,
+                                  out_rows ? out_rows + r0 : nullptr))
+            return rc;
+    }
+    return eval_acc_read(c, false, out_sum);
+}
+
+int vaeb_marginal_ll_resident(vaeb_ctx* c, int32_t K, double* out_sum) {
+    if (!c || !out_sum) return fail(VAEB_ERR_ARG, "null argument");
+    if (is_bf16(c)) return fail(VAEB_ERR_ARG, "vaeb_marginal_ll_resident is served by fp32 contexts");
+    if (c->nval <= 0) return fail(VAEB_ERR_STATE, "vaeb_set_valid_data has not been called");
+    int epar = 0;
+    if (int rc = iw_begin(c, c->nval, K, &epar)) return rc;
+    const vaeb_config& g = c->c;
+    int64_t lo = 0, rows = 0;
+    valid_share(c, &lo, &rows);
+    const int chunk = g.max_eval_rows;
+    for (int64_t r0 = lo; r0 < lo + rows; r0 += chunk) {
+        const int m = (int)std::min<int64_t>(chunk, lo + rows - r0);
+        if (int rc = iw_chunk_f32(c, epar, c->xval + r0 * g.D, m, r0, K, c->eps_in ? c->eps_in + r0 * g.Z : nullptr,
+                                  c->nval, nullptr))
+            return rc;
+    }
+    return eval_acc_read(c, true, out_sum);
 }
 
 int vaeb_comm_unique_id(uint8_t out_id[128]) {

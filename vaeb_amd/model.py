@@ -307,6 +307,34 @@ class VAEB:
             y = (y.astype(np.float64) + np.exp(ls.astype(np.float64)) * np.random.standard_normal(y.shape))
         return y[0] if one else y
 
+    def encoder(self, x):
+        """VAEB.encoder (VAEB.py:245-251) evaluated at x: (mu, log_var), each [n x Z] (1-D for a
+        1-D x)."""
+        x = np.asarray(x, np.float32)
+        mu, lv = self._ctx.encode(np.atleast_2d(x))
+        return (mu[0], lv[0]) if x.ndim == 1 else (mu, lv)
+
+    def _push_sample_eps(self, rows, n_samples):
+        # one srng.normal draw per sample (VAEB.py:280), rows stacked sample-major
+        self._ctx.push_eps(np.concatenate([self._stream.draw(rows, self.n_latent)
+                                           for _ in range(n_samples)], axis=1))
+
+    def marginal_likelihood(self, x, n_samples=50, per_row=False):
+        """Extension (no reference counterpart): the n_samples-sample importance-weighted
+        estimate of sum_i log p(x_i) with the encoder as the proposal -- the sum over the rows
+        of x, like validate; per_row=True returns (sum, per-row values [n])."""
+        x = np.atleast_2d(np.asarray(x, np.float32))
+        if self._stream is not None:
+            self._push_sample_eps(x.shape[0], int(n_samples))
+        return self._ctx.marginal_ll(x, int(n_samples), rows=per_row)
+
+    def marginal_likelihood_resident(self, n_samples=50):
+        """marginal_likelihood over the resident validation set (set_validation_data): the sum
+        over its rows, all-reduced over the ranks."""
+        if self._stream is not None:
+            self._push_sample_eps(self._nvalid, int(n_samples))
+        return self._ctx.marginal_ll_resident(int(n_samples))
+
     def decoder(self, z):
         """VAEB.decoder (VAEB.py:253-265) evaluated at given latents z [n x Z]: (mu,
         log_sigma) for the continuous decoder, y for the Bernoulli one."""
