@@ -101,7 +101,28 @@ int vaeb_get_fv_state(vaeb_ctx* ctx, float* mu, float* sigma,
 
 /* Noise for the reparameterisation (VAEB.py:41-47).  PHILOX: counter-based normals
  * keyed by (seed, step, global row, l, j), world-size invariant.  HOST: the caller
- * pushes eps [L x rows x Z] before each update/validate chunk (parity mode). */
+ * pushes eps [L x rows x Z] before each update/validate chunk (parity mode).
+ *
+ * The exact key (oracle/philox.py draws the same numbers on the host; tests/test_gpu_philox.py
+ * compares).  One draw is Philox4x32-10 on a 128-bit counter (c0, c1, c2, c3) under the key
+ * (low word of seed, high word of seed):
+ *   c0      (uint32) row.  Training: batch_index * B_global + row_offset + m, m the row inside
+ *           this rank's B.  vaeb_validate / vaeb_reconstruct_sampled / vaeb_marginal_ll: the
+ *           row's index in the x passed to the call (not in the device chunk); the resident
+ *           calls: the row's index in the resident set.
+ *   c1      l * Z + j for sample l, latent j (evaluation streams: L of the context for
+ *           vaeb_validate, one sample per stream otherwise, so c1 = j).
+ *   c2, c3  low and high word of  step ^ (evaluation ? 1 << 63 : 0) ^ (stream << 40):
+ *           stream 0 for training and validation, s for the s-th sample (1-based) of
+ *           vaeb_reconstruct_sampled, k + 1 for importance sample k of vaeb_marginal_ll.
+ *   eps = sqrt(-2 ln u1) cos(2 pi u2),  u1 = ((out0 >> 8) + 1) / 2^24,  u2 = (out1 >> 8) / 2^24.
+ * VAEB_EST_FVS weight noise: parameter i (arena order) is normal i & 3 of group g = i >> 2 with
+ * counter (uint32 g, 0x40000000 | g >> 32, step low, step high): r0 cos t0, r0 sin t0, r1 cos t1,
+ * r1 sin t1, r from out0 / out2 and t from out1 / out3 as above.
+ * Limits of this layout: rows are taken mod 2^32; L * Z < 2^30 (c1 bit 30 marks the weight
+ * noise); the stream field occupies bits 40..62 of the step word, so streams and steps >= 2^40
+ * overlap; hence n_samples, K <= 2^20.  Training steps draw at the counter and advance it by
+ * one; evaluation calls draw at the current counter and leave it. */
 int vaeb_set_eps_mode(vaeb_ctx* ctx, int32_t mode, uint64_t seed);
 int vaeb_push_eps(vaeb_ctx* ctx, const float* eps, int64_t rows, int32_t L);
 /* VAEB_EST_FVS in host eps mode: the standard normals zeta [P] (arena order) of the next
