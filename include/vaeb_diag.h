@@ -52,6 +52,16 @@ int vaeb_comm_info(vaeb_ctx* ctx, int32_t* rccl_version, int32_t* dp_overlap, in
 int vaeb_dp_plan(const vaeb_config* cfg, int32_t world, int32_t rank, int32_t sharded, int32_t bucket,
                  int64_t* out_P, int64_t* runs, int32_t* out_nrun, int64_t* own, int32_t* out_nown,
                  int32_t* out_book, int64_t* foreign, int32_t* out_nforeign);
+/* Host-only diagnostics (no device call, no context): the tiling of the deferred dW2 (| dW6)
+ * weight gradient -- the (H + 1) x (D g) matrix [hd | 1]^T [dA2 (| dA6)], g = 2 for the Gaussian
+ * decoder -- exactly as the training step of cfg (D, H, Z, B, decoder) and its flush launch
+ * compute it (vaeb_hip.hip w2_plan).  Outputs (each may be NULL): the tile width in columns;
+ * paired = 1 when no width fits one tile per free CU and two 32-wide tiles share a workgroup;
+ * the number of tile workers; the CUs the encoder's workgroups leave free; the [W2 | W6] column
+ * boundary (D; 0 for the Bernoulli decoder); ranges[4 * worker] = (row0, row1, col0, col1),
+ * half-open and clipped to the matrix, for at most `cap` workers. */
+int vaeb_dw2_plan(const vaeb_config* cfg, int32_t* out_width, int32_t* out_paired, int32_t* out_workers,
+                  int32_t* out_free_cus, int32_t* out_split, int32_t* ranges, int32_t cap);
 /* Diagnostics: the world > 1 device path of the sharded data-parallel optimizer on ONE GPU.
  * Runs rank `rank` of a `world`-rank step's optimizer for one gradient bucket (0 = A, 1 = B,
  * 2 = all; as vaeb_dp_plan) on a context WITHOUT a communicator, with the collectives of

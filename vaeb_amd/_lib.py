@@ -40,7 +40,7 @@ EXPORTS = [
 ]
 DIAG_EXPORTS = ["vaeb_profile_steps", "vaeb_kernel_name", "vaeb_debug_timeline", "vaeb_test_gemm_bf16",
                 "vaeb_bench_gemm_bf16", "vaeb_graph_status", "vaeb_comm_info", "vaeb_time_update_many", "vaeb_busy",
-                "vaeb_dp_plan", "vaeb_dp_rank_update", "vaeb_get_shadow"]
+                "vaeb_dp_plan", "vaeb_dp_rank_update", "vaeb_get_shadow", "vaeb_dw2_plan"]
 GRAPH_MODES = {0: "off", 1: "not_captured", 2: "replay", 3: "eager_fallback"}
 AE_MAX_LAYERS = 8
 AE_BINARY, AE_CONT = 0, 1
@@ -141,6 +141,8 @@ def load():
                           ctypes.POINTER(_I64), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
                           ctypes.POINTER(_I64), ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
         "vaeb_dp_rank_update": ([_P] + [ctypes.c_int32] * 3 + [_F, _I64, _F, ctypes.c_int32], ctypes.c_int),
+        "vaeb_dw2_plan": ([ctypes.POINTER(VaebConfig)] + [ctypes.POINTER(ctypes.c_int32)] * 6 + [ctypes.c_int32],
+                          ctypes.c_int),
         "vaeb_get_shadow": ([_P, ctypes.POINTER(ctypes.c_uint16), _I64], ctypes.c_int),
         "vaeb_time_update_many": ([_P, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, _F,
                                    ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
@@ -198,6 +200,23 @@ def dp_plan(D, H, Z, world, rank, bucket=2, sharded=True, decoder=DEC_BERNOULLI)
             "own": [(own[2 * k], own[2 * k + 1]) for k in range(nown.value)],
             "book": bool(book.value),
             "foreign": [(foreign[2 * k], foreign[2 * k + 1]) for k in range(nfor.value)]}
+
+
+def dw2_plan(D, H, Z, B, decoder=DEC_BERNOULLI):
+    """The deferred dW2 (| dW6) tiling as the library computes it (vaeb_dw2_plan; host only, no
+    GPU).  Returns a dict: width, paired (bool), workers, free_cus, split (the [W2 | W6] column
+    boundary, 0 for Bernoulli), ranges [(row0, row1, col0, col1)] per worker, half-open."""
+    lib = load()
+    cfg = VaebConfig()
+    cfg.D, cfg.H, cfg.Z, cfg.B, cfg.B_global, cfg.L = D, H, Z, B, B, 1
+    cfg.decoder = decoder
+    width, paired, workers, free, split = (ctypes.c_int32() for _ in range(5))
+    check(lib.vaeb_dw2_plan(ctypes.byref(cfg), ctypes.byref(width), ctypes.byref(paired), ctypes.byref(workers),
+                            ctypes.byref(free), ctypes.byref(split), None, 0))
+    r = (ctypes.c_int32 * (4 * workers.value))()
+    check(lib.vaeb_dw2_plan(ctypes.byref(cfg), None, None, None, None, None, r, workers.value))
+    return {"width": width.value, "paired": bool(paired.value), "workers": workers.value, "free_cus": free.value,
+            "split": split.value, "ranges": [tuple(r[4 * k:4 * k + 4]) for k in range(workers.value)]}
 
 
 def fptr(a: np.ndarray):

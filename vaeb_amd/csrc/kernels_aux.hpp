@@ -577,7 +577,7 @@ DEV void wgrad_body(const WA& p, const WGroup& g, int bid, float (*sa)[kWP], flo
                     const int* gate = nullptr) {
     const int gv = gate ? ld_launch_const(gate) : 1;
     static_assert(NWV == 4 || NWV == 8, "wgrad: 4 or 8 waves");
-    static_assert(TS == 1 || TS == 2 || TS == 4, "wgrad: 16, 32 or 64 columns per tile");
+    static_assert(TS >= 1 && TS <= 4, "wgrad: 16, 32, 48 or 64 columns per tile");
     constexpr int kWTS = TS, kWTJ = 16 * TS;
     constexpr int NTH = 64 * NWV;
     // the thread's index in its tile worker (a 1024-thread workgroup can run two 512-thread

@@ -242,7 +242,7 @@ struct PEncCT : PEnc {
 // red_ext (EXTRED): the K-slice reduction buffer (64 NWV CT f32x4) from the caller -- the
 // deferred-dW2 encoder carves it from the LDS its dW2 workers use (enc_latent16_w2_kernel).
 template <int NCT, int GCH, bool FV, int HO, int CT = 1, int NWV = 8, bool EXTRED = false>
-DEV void enc_latent_body(const StepArgs& a, const FvFold& fvf, f32x4* red_ext = nullptr) {
+DEV void enc_latent_body(const StepArgs& a, const FvFold& fvf, f32x4* red_ext = nullptr, int y0 = 0) {
     static_assert(NWV == 8 || (HO != 0 && !FV), "16 waves: no ticketed reducer, no FV stream");
     constexpr bool AT = HO == 1;
     constexpr int NTH = 64 * NWV;
@@ -262,8 +262,9 @@ DEV void enc_latent_body(const StepArgs& a, const FvFold& fvf, f32x4* red_ext = 
     // more dependent scalar round trip ahead of every workgroup's first operand load)
     const int nctH = (a.H + 16 * CT - 1) / (16 * CT);
     const int gxE = a.Mbp >> 4;   // grid: (Mbp / 16, nctH (+ FV stream rows))
-    if (FV && (int)blockIdx.y >= nctH) {
-        fv_stream_block(fvf, (blockIdx.y - nctH) * gxE + blockIdx.x, fvf.rows * gxE, reinterpret_cast<double*>(red));
+    const int gy = (int)blockIdx.y - y0;   // y0: the encoder's first grid row (enc_latent16_w2_kernel)
+    if (FV && gy >= nctH) {
+        fv_stream_block(fvf, (gy - nctH) * gxE + blockIdx.x, fvf.rows * gxE, reinterpret_cast<double*>(red));
         return;
     }
     VAEB_STAMP(a, 0);
@@ -271,7 +272,7 @@ DEV void enc_latent_body(const StepArgs& a, const FvFold& fvf, f32x4* red_ext = 
     p.prepare();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int li = lane & 15, q = lane >> 4;
-    const int lin = xcd_remap(blockIdx.x + blockIdx.y * gxE, gxE * nctH);
+    const int lin = xcd_remap(blockIdx.x + gy * gxE, gxE * nctH);
     const int bx = lin % gxE, by = lin / gxE;
     const int m0 = bx * 16, n0 = by * 16 * CT;
     const int Z = a.Z, H = a.H;
@@ -506,24 +507,36 @@ __global__ __launch_bounds__(1024) void enc_latent16_kernel(StepArgs a) {
 // The same encoder with the PREVIOUS step's dW2 (| dW6) tiles + Adagrad on the CUs it leaves
 // idle (the deferred dW2, vaeb_hip.hip vaeb_ctx::dw2_defer): the encoder's 112 workgroups
 // take 112 of 256 CUs at MNIST, and W2 is first read again by this step's decoder launch.
-// Grid rows >= rows_enc are dW2 workers, two 64 x (16 TS) tiles each (waves 0-7 and 8-15,
-// wgrad_body's 512-thread tile on its own half of the LDS); they read hd / dA2 of the previous
-// step (intact until this step's decoder launch) and theta from the other arena, and write
-// W2' into the arena this step reads (which the encoder does not touch).  *pend == 0
+// Grid rows [y_w2, y_w2 + rows_w2) are dW2 workgroups, the encoder's start at row y_enc.  A
+// worker is wgrad_body's 512-thread 64 x (16 TS) tile: NW = 1 runs one per workgroup (waves
+// 8-15 leave at entry), so no CU stages the hd panel twice; the host (w2_plan) picks the
+// narrowest TS whose tile count fits the CUs the encoder leaves free and puts the worker rows
+// first in dispatch order (they are the launch's longest chain).  NW = 2 (the paired form, where
+// no width fits; VAEB_DW2_PAIRED=1): two 32-wide tiles per workgroup, waves 0-7 and 8-15, each on
+// its own half of the LDS.  The tile width does not enter any sum: an output element always
+// accumulates its even 16-row K chunks on waves 0-3, its odd ones on waves 4-7, odd added into
+// even (wgrad_body NWV = 8), so every form gives the same bits.  The workers read hd / dA2 of
+// the previous step (intact until this step's decoder launch) and theta from the other arena,
+// and write W2' into the arena this step reads (which the encoder does not touch).  *pend == 0
 // (nothing pending: the first step, or a flush since) drops their stores.  LDS: two tiles' (sa,
-// sb) = 139 KB, the encoder's K-slice reduction buffer (32 KB) carved from the same block.
-template <int NCT, int GCH, int HO, int CT, bool VEC, int TS>
-__global__ __launch_bounds__(1024) void enc_latent16_w2_kernel(StepArgs a, WGradArgs w, const int* pend, int rows_enc) {
+// sb) = 139 KB in both forms (it also keeps a second workgroup off the CU), the encoder's
+// K-slice reduction buffer (32 KB) carved from the same block.
+template <int NCT, int GCH, int HO, int CT, bool VEC, int TS, int NW>
+__global__ __launch_bounds__(1024) void enc_latent16_w2_kernel(StepArgs a, WGradArgs w, const int* pend, int y_enc,
+                                                               int y_w2, int rows_w2) {
     __shared__ __attribute__((aligned(16))) float lds[4 * kWKB * kWP];
     static_assert(sizeof(float) * 4 * kWKB * kWP >= sizeof(f32x4) * 64 * 16 * CT, "LDS union");
-    if ((int)blockIdx.y >= rows_enc) {
+    static_assert(NW == 1 || NW == 2, "one or two dW2 workers per workgroup");
+    const int wy = (int)blockIdx.y - y_w2;
+    if (wy >= 0 && wy < rows_w2) {
         const int half = (int)threadIdx.x >> 9;
-        const int bid = 2 * (((int)blockIdx.y - rows_enc) * (a.Mbp >> 4) + (int)blockIdx.x) + half;
+        if (NW == 1 && half) return;
+        const int bid = NW * (wy * (a.Mbp >> 4) + (int)blockIdx.x) + (NW == 2 ? half : 0);
         float (*sa)[kWP] = reinterpret_cast<float(*)[kWP]>(lds + half * 2 * kWKB * kWP);
         wgrad_body<VEC, 8, TS>(w, w.g[0], bid, sa, sa + kWKB, pend);
         return;
     }
-    enc_latent_body<NCT, GCH, false, HO, CT, 16, true>(a, FvFold{}, reinterpret_cast<f32x4*>(lds));
+    enc_latent_body<NCT, GCH, false, HO, CT, 16, true>(a, FvFold{}, reinterpret_cast<f32x4*>(lds), y_enc);
 }
 
 // ----------------------------------------------------------------------------- P4'

@@ -181,6 +181,7 @@ struct vaeb_ctx {
     // fp32 LB / LA, no communicator, 16-wave encoder, the latent backward deferred too (ho_dz 2:
     // dw2_deferred).  VAEB_DW2_DEFER=0: dW2 in the dhd launch.
     bool dw2_defer = true;
+    bool dw2_paired = false;      // VAEB_DW2_PAIRED=1: always two 32-wide dW2 tiles per workgroup (w2_plan)
     int* w2pend = nullptr;        // device: 1 = a step's dW2 is pending (set by its dhd launch)
     bool w2_dirty = false;        // host: a step was enqueued since the last flush
     bool w2_graph = false;        // host: the captured graphs hold deferred-dW2 steps (run_steps sets w2_dirty)
@@ -302,7 +303,32 @@ struct W2Launch {
     WGradArgs w;
     bool vec;
     const int* pend;
+    int width;     // tile columns (w2_plan)
+    bool paired;   // two tiles per workgroup, after the encoder rows
 };
+
+// The deferred dW2's tiling (latent.hpp enc_latent16_w2_kernel).  One 64 x width tile per
+// workgroup, each on a CU of its own beside the encoder's `enc_wgs` workgroups: the narrowest of
+// 32, 48 and 64 columns whose tile count fits the CUs left free (narrower tiles stream fewer
+// theta / Adagrad / panel bytes through one CU's load path; MNIST 784-500: 17 x 8 = 136 tiles
+// of 48 beside 112 encoder workgroups).  Where none fits (or VAEB_DW2_PAIRED=1): 32-wide tiles,
+// two per workgroup.  rows = H + 1 (the bias row), cols = D (Gaussian: [W2 | W6] = 2 D).
+// wide64: 64 columns are a candidate -- only with 16-byte accesses (the scalar epilogue's
+// per-element offsets, theta and Adagrad state of 64 columns do not fit 128 VGPRs).
+constexpr int kCUs = 256;
+struct W2Plan {
+    int width, paired, tiles_i, tiles_j;   // tile (row block i, column block j) = worker i * tiles_j + j
+};
+W2Plan w2_plan(int rows, int cols, int enc_wgs, bool force_paired, bool wide64) {
+    const int ti = cdiv(rows, kWT);
+    if (!force_paired)
+        for (int w : {32, 48, 64}) {
+            if (w == 64 && !wide64) break;
+            const int tj = cdiv(cols, w);
+            if (ti * tj <= kCUs - enc_wgs) return W2Plan{w, 0, ti, tj};
+        }
+    return W2Plan{kWTJ_P5, 1, ti, cdiv(cols, kWTJ_P5)};
+}
 
 // The folded latent hand-offs: counted fixed-point atomics (latent.hpp fx_*) or slabs +
 // ticket + reducer.  The returning adds to one accumulator serialise at the memory side, so
@@ -426,19 +452,36 @@ void launch_enc_latent_ct(hipStream_t s, dim3 g1, const StepArgs& a, const FvFol
     }
 }
 // The 16-wave encoder with the deferred dW2 workers (w2: the previous step's dW2 group) in
-// ceil(ntile / 2 / (Mbp / 16)) extra grid rows.
+// ceil(workgroups / (Mbp / 16)) extra grid rows: ahead of the encoder rows with one tile per
+// workgroup, behind them in the paired form (and in the timeline build, whose stamps index the
+// encoder's workgroups from 0).
+template <int HO, int CT, int TS, int NW>
+void launch_enc16_w2_ts(hipStream_t s, dim3 g1, const StepArgs& a, const W2Launch& w2) {
+    const int rows_enc = (int)g1.y, rows_w2 = cdiv(cdiv(w2.w.total_wgs, NW), (int)g1.x);
+#ifdef VAEB_TIMELINE
+    const bool first = false;
+#else
+    const bool first = NW == 1;
+#endif
+    const int y_enc = first ? rows_w2 : 0, y_w2 = first ? 0 : rows_enc;
+    const dim3 g(g1.x, rows_enc + rows_w2);
+    if constexpr (TS == 4) {   // 64 columns: planned only with 16-byte accesses (w2_plan)
+        if (a.Z <= 16) hipLaunchKernelGGL((enc_latent16_w2_kernel<1, 4, HO, CT, true, TS, NW>), g, dim3(1024), 0, s, a, w2.w, w2.pend, y_enc, y_w2, rows_w2);
+        else hipLaunchKernelGGL((enc_latent16_w2_kernel<2, 4, HO, CT, true, TS, NW>), g, dim3(1024), 0, s, a, w2.w, w2.pend, y_enc, y_w2, rows_w2);
+    } else if (a.Z <= 16) {
+        if (w2.vec) hipLaunchKernelGGL((enc_latent16_w2_kernel<1, 4, HO, CT, true, TS, NW>), g, dim3(1024), 0, s, a, w2.w, w2.pend, y_enc, y_w2, rows_w2);
+        else hipLaunchKernelGGL((enc_latent16_w2_kernel<1, 4, HO, CT, false, TS, NW>), g, dim3(1024), 0, s, a, w2.w, w2.pend, y_enc, y_w2, rows_w2);
+    } else {
+        if (w2.vec) hipLaunchKernelGGL((enc_latent16_w2_kernel<2, 4, HO, CT, true, TS, NW>), g, dim3(1024), 0, s, a, w2.w, w2.pend, y_enc, y_w2, rows_w2);
+        else hipLaunchKernelGGL((enc_latent16_w2_kernel<2, 4, HO, CT, false, TS, NW>), g, dim3(1024), 0, s, a, w2.w, w2.pend, y_enc, y_w2, rows_w2);
+    }
+}
 template <int HO, int CT>
 void launch_enc16_w2(hipStream_t s, dim3 g1, const StepArgs& a, const W2Launch& w2) {
-    const int rows = (int)g1.y;
-    const dim3 g(g1.x, g1.y + cdiv(cdiv(w2.w.total_wgs, 2), (int)g1.x));
-    constexpr int TS = kWTJ_P5 / 16;
-    if (a.Z <= 16) {
-        if (w2.vec) hipLaunchKernelGGL((enc_latent16_w2_kernel<1, 4, HO, CT, true, TS>), g, dim3(1024), 0, s, a, w2.w, w2.pend, rows);
-        else hipLaunchKernelGGL((enc_latent16_w2_kernel<1, 4, HO, CT, false, TS>), g, dim3(1024), 0, s, a, w2.w, w2.pend, rows);
-    } else {
-        if (w2.vec) hipLaunchKernelGGL((enc_latent16_w2_kernel<2, 4, HO, CT, true, TS>), g, dim3(1024), 0, s, a, w2.w, w2.pend, rows);
-        else hipLaunchKernelGGL((enc_latent16_w2_kernel<2, 4, HO, CT, false, TS>), g, dim3(1024), 0, s, a, w2.w, w2.pend, rows);
-    }
+    if (w2.paired) launch_enc16_w2_ts<HO, CT, kWTJ_P5 / 16, 2>(s, g1, a, w2);
+    else if (w2.width == 32) launch_enc16_w2_ts<HO, CT, 2, 1>(s, g1, a, w2);
+    else if (w2.width == 48) launch_enc16_w2_ts<HO, CT, 3, 1>(s, g1, a, w2);
+    else launch_enc16_w2_ts<HO, CT, 4, 1>(s, g1, a, w2);
 }
 
 // The slab-only encoder (HO 3: partials summed by the decoder launch, CT = 2, no FV) and the
@@ -692,12 +735,24 @@ WGroup make_group(vaeb_ctx* c, const float* at, int ld_at, int klim, int at_is_x
 
 // The dW2 (| dW6) weight-gradient group -- [hd | 1]^T [dA2 (| dA6)] -- as launch arguments
 // whose tiles start at block `base`, with the optimizer `opt`.
-int w2_args(vaeb_ctx* c, const StepArgs& a, const OptArgs& opt, int base, WGradArgs& w, bool& vec) {
+int w2_args(vaeb_ctx* c, const StepArgs& a, const OptArgs& opt, int base, WGradArgs& w, bool& vec, int tw = kWTJ_P5) {
     const bool gs = gaussian(c);
     const int bo = gs ? 6 : 5;
     WGroup g4 = make_group(c, c->hd, a.H, a.Me, 0, a.H, c->dA2, a.D, a.D, gs ? c->dA6 : nullptr, a.D, gs ? a.D : 0,
                            a.Me, 4, bo + 4, gs ? 5 : -1, gs ? bo + 5 : -1);
-    return prep_wgrad(c, &g4, 1, opt, nullptr, a, base, w, vec, kWTJ_P5);
+    return prep_wgrad(c, &g4, 1, opt, nullptr, a, base, w, vec, tw);
+}
+// The deferred dW2's tiling for the training step on `a` (its encoder grid: enqueue_forward).
+W2Plan w2_plan_for(const vaeb_ctx* c, const StepArgs& a) {
+    int ct = 1;
+    enc_form(c, a, FvFold{}, nullptr, &ct, nullptr);
+    // prep_wgrad's conditions on the dW2 group's widths and arena offsets for 16-byte accesses
+    // (its pointers are device allocations, always aligned)
+    const bool gs = gaussian(c);
+    const int bo = gs ? 6 : 5;
+    const bool vec = a.H % 4 == 0 && a.D % 4 == 0 && c->off[4] % 4 == 0 && c->off[bo + 4] % 4 == 0 &&
+                     (!gs || (c->off[5] % 4 == 0 && c->off[bo + 5] % 4 == 0));
+    return w2_plan(a.H + 1, (gs ? 2 : 1) * a.D, (a.Mbp / 16) * cdiv(a.H, 16 * ct), c->dw2_paired, vec);
 }
 
 // Whether the step on `a` defers its dW2 into the next step's encoder launch (vaeb_ctx::dw2_defer).
@@ -727,10 +782,18 @@ int w2_flush(vaeb_ctx* c) {
     StepArgs a = make_args(c, par, c->c.B, MODE_TRAIN, c->data, true);
     WGradArgs w;
     bool vec;
-    if (int rc = w2_args(c, a, make_opt(c, par ^ 1, true, c->c.keep_grads != 0), 0, w, vec)) return rc;
+    const int tw = w2_plan_for(c, a).width;   // the width of the deferred launch this one replaces
+    if (int rc = w2_args(c, a, make_opt(c, par ^ 1, true, c->c.keep_grads != 0), 0, w, vec, tw)) return rc;
     w.dbg = nullptr;
-    if (vec) hipLaunchKernelGGL((w2_flush_kernel<true, kWTJ_P5 / 16>), dim3(w.total_wgs), dim3(512), 0, c->s, w, c->w2pend);
-    else hipLaunchKernelGGL((w2_flush_kernel<false, kWTJ_P5 / 16>), dim3(w.total_wgs), dim3(512), 0, c->s, w, c->w2pend);
+    if (tw == 64 && !vec) return fail(VAEB_ERR_ARG, "internal: 64-wide dW2 tiles need 16-byte accesses");
+    auto go = [&](auto TS) {
+        constexpr int ts = decltype(TS)::value;
+        if (vec) hipLaunchKernelGGL((w2_flush_kernel<true, ts>), dim3(w.total_wgs), dim3(512), 0, c->s, w, c->w2pend);
+        else if constexpr (ts < 4) hipLaunchKernelGGL((w2_flush_kernel<false, ts>), dim3(w.total_wgs), dim3(512), 0, c->s, w, c->w2pend);
+    };
+    if (tw == 32) go(std::integral_constant<int, 2>{});
+    else if (tw == 48) go(std::integral_constant<int, 3>{});
+    else go(std::integral_constant<int, 4>{});
     CHECK_LAUNCH();
     HIP_TRY(hipMemsetAsync(c->w2pend, 0, sizeof(int), c->s));
     return 0;
@@ -1012,7 +1075,11 @@ int enqueue_train_step(vaeb_ctx* c, int par, bool prof, bool fresh = true, int d
     const bool w2d = dw2_deferred(c, a);
     W2Launch w2{};
     if (w2d) {
-        if (int rc = w2_args(c, a, make_opt(c, par ^ 1, true, g.keep_grads != 0), 0, w2.w, w2.vec)) return rc;
+        const W2Plan pl = w2_plan_for(c, a);
+        w2.width = pl.width;
+        w2.paired = pl.paired != 0;
+        if (int rc = w2_args(c, a, make_opt(c, par ^ 1, true, g.keep_grads != 0), 0, w2.w, w2.vec, pl.width)) return rc;
+        if (pl.width == 64 && !w2.vec) return fail(VAEB_ERR_ARG, "internal: 64-wide dW2 tiles need 16-byte accesses");
         // (timeline build: the dW2 tiles stamp at logical ids 256 + tile of the encoder launch)
         w2.w.dbg = c->dbg ? c->dbg + (size_t)c->dbg_slot * kDbgWG * 8 + 256 * 8 : nullptr;
         w2.pend = c->w2pend;
@@ -1366,6 +1433,7 @@ int vaeb_create(const vaeb_config* cfg, vaeb_ctx** out) {
     if (const char* fb = getenv("VAEB_FOLD_BWD")) c->fold_bwd = atoi(fb) != 0;
     if (const char* bd = getenv("VAEB_BWD_DEFER")) c->bwd_defer = atoi(bd) != 0;
     if (const char* wd = getenv("VAEB_DW2_DEFER")) c->dw2_defer = atoi(wd) != 0;
+    if (const char* wp = getenv("VAEB_DW2_PAIRED")) c->dw2_paired = atoi(wp) != 0;
     if (const char* ah = getenv("VAEB_ATOMIC_HO")) c->atomic_ho = atoi(ah) != 0 ? 1 : 0;
     if (const char* er = getenv("VAEB_ENC_RED")) c->enc_red = atoi(er) != 0 ? 1 : 0;
     if (const char* bk = getenv("VAEB_BF_FORK")) c->bf_fork = atoi(bk) != 0;
@@ -2496,6 +2564,39 @@ int vaeb_dp_plan(const vaeb_config* cfg, int32_t world, int32_t rank, int32_t sh
     put(o, own, out_nown);
     if (out_book) *out_book = o.book;
     put(dp_foreign_range(&c, bk), foreign, out_nforeign);
+    return 0;
+}
+
+int vaeb_dw2_plan(const vaeb_config* cfg, int32_t* out_width, int32_t* out_paired, int32_t* out_workers,
+                  int32_t* out_free_cus, int32_t* out_split, int32_t* ranges, int32_t cap) {
+    if (!cfg) return fail(VAEB_ERR_ARG, "bad plan arguments");
+    if (cfg->D <= 0 || cfg->H <= 0 || cfg->Z <= 0 || cfg->B <= 0) return fail(VAEB_ERR_ARG, "dimensions must be positive");
+    // a host-only context (as vaeb_dp_plan): the same code the step and the flush run
+    vaeb_ctx c;
+    c.c = *cfg;
+    set_arena_layout(&c);
+    StepArgs a{};
+    a.D = cfg->D; a.H = cfg->H; a.Z = cfg->Z;
+    a.Mb = cfg->B; a.Mbp = r16(cfg->B);
+    int ct = 1;
+    enc_form(&c, a, FvFold{}, nullptr, &ct, nullptr);
+    const W2Plan pl = w2_plan_for(&c, a);
+    const int rows = a.H + 1, cols = (gaussian(&c) ? 2 : 1) * a.D, n = pl.tiles_i * pl.tiles_j;
+    if (out_width) *out_width = pl.width;
+    if (out_paired) *out_paired = pl.paired;
+    if (out_workers) *out_workers = n;
+    if (out_free_cus) *out_free_cus = kCUs - (a.Mbp / 16) * cdiv(a.H, 16 * ct);
+    if (out_split) *out_split = gaussian(&c) ? a.D : 0;
+    if (ranges) {
+        if (cap < n) return fail(VAEB_ERR_ARG, "%d tile ranges do not fit %d", n, cap);
+        for (int lt = 0; lt < n; ++lt) {   // wgrad_body's i0 / j0 of worker lt, clipped to the matrix
+            const int i0 = (lt / pl.tiles_j) * kWT, j0 = (lt % pl.tiles_j) * pl.width;
+            ranges[4 * lt] = i0;
+            ranges[4 * lt + 1] = std::min(i0 + kWT, rows);
+            ranges[4 * lt + 2] = j0;
+            ranges[4 * lt + 3] = std::min(j0 + pl.width, cols);
+        }
+    }
     return 0;
 }
 
