@@ -74,6 +74,22 @@ def test_error_reporting_without_gpu(lib):
     assert b"dimensions" in L.vaeb_last_error()
     cfg.D, cfg.estimator, cfg.L = 5, 2, 2   # FV with L > 1 is rejected (VAEB.py:361 shadowing bug)
     assert L.vaeb_create(ctypes.byref(cfg), ctypes.byref(h)) == -1
+    # the 16-bit engines keep the LA estimator's per-sample terms in eight registers
+    # (step_bf16.hpp la[8]): L = 9 is VAEB_ERR_ARG, checked before the device is touched
+    for dtype in (_lib.DTYPE_BF16, _lib.DTYPE_F16):
+        cfg = _lib.VaebConfig()
+        cfg.D, cfg.H, cfg.Z, cfg.B, cfg.L = 128, 64, 16, 40, 9
+        cfg.estimator, cfg.dtype = _lib.EST_LA, dtype
+        h = ctypes.c_void_p()
+        assert L.vaeb_create(ctypes.byref(cfg), ctypes.byref(h)) == -1
+        assert b"L <= 8" in L.vaeb_last_error()
+        assert not h.value
+        # LB has no such limit: the same config passes the argument checks (and then needs a GPU)
+        cfg.estimator = _lib.EST_LB
+        rc = L.vaeb_create(ctypes.byref(cfg), ctypes.byref(h))
+        assert rc != -1 and (rc == 0 or b"L <= 8" not in L.vaeb_last_error()), (rc, L.vaeb_last_error())
+        if rc == 0:
+            assert L.vaeb_destroy(h) == 0
     major, minor = ctypes.c_int32(), ctypes.c_int32()
     assert L.vaeb_version(ctypes.byref(major), ctypes.byref(minor)) == 0
 

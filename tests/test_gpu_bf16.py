@@ -94,6 +94,9 @@ CASES = [
     ("bern_LB_longk", dict(D=512, H=256, Z=32), 1024),
     ("gauss_LA_L2_longk", dict(D=256, H=256, Z=16, continuous=True, estimator="LA", L=2), 1024),
     ("bern_LB_longk_tails", dict(D=520, H=264, Z=24), 1100),
+    # L > 2: the last L the LA estimator's per-sample registers hold (step_bf16.hpp la[8]), an odd L
+    ("bern_LA_L8", dict(D=128, H=64, Z=16, estimator="LA", L=8), 40),
+    ("gauss_LB_L5", dict(D=128, H=64, Z=8, continuous=True, L=5), 72),
 ]
 
 

@@ -66,6 +66,9 @@ CASES = [
     ("gauss_LA_L2", dict(D=256, H=256, Z=16, continuous=True, estimator="LA", L=2), 512),
     ("bern_LB_tails", dict(D=520, H=264, Z=24), 1100),
     ("bern_mean_map", dict(D=512, H=256, Z=32, objective="mean_map"), 1024),
+    # L > 2: the last L the LA estimator's per-sample registers hold (step_bf16.hpp la[8]), an odd L
+    ("bern_LA_L8", dict(D=128, H=64, Z=16, estimator="LA", L=8), 40),
+    ("gauss_LB_L5", dict(D=128, H=64, Z=8, continuous=True, L=5), 72),
 ]
 
 
