@@ -1,6 +1,6 @@
 """Data-parallel decomposition of the SGVB step, checked with real torch.distributed
 (gloo, world_size 2, CPU).  This is the host orchestration the HIP path implements with
-one RCCL all-reduce per step (vaeb_hip.hip: P8 grads -> ncclAllReduce([grads | SGVB]) ->
+one RCCL all-reduce per step (engine_f32.inc: P8 grads -> ncclAllReduce([grads | SGVB]) ->
 adagrad_kernel): every rank computes the data gradient of its rows, the SUM is
 all-reduced, the -theta prior is added once after the reduce, and every rank applies the
 identical Adagrad update.  The result must equal the single-process step on the
@@ -90,7 +90,7 @@ def test_strong_scaling_row_map():
 
 
 def _shard_rank_main(rank, world, port, q):
-    """Two steps of the sharded optimizer (vaeb_hip.hip dp_reduce_update) in torch.distributed
+    """Two steps of the sharded optimizer (dp_buckets.inc dp_reduce_update) in torch.distributed
     (gloo): each rank's data gradient is summed and sliced to its shard (the reduce-scatter)
     and to the replicated remainders (the all-reduce); the rank applies the prior + Adagrad to
     its shard and the remainders only, keeping Adagrad state for those alone; the theta'

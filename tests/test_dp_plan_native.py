@@ -2,7 +2,7 @@
 "check the C++ plan, not its Python mirror").
 
 `vaeb_dp_plan` (include/vaeb_diag.h) runs the same `dp_bucket_*_runs`, `dp_shard_len`,
-`dp_opt_range` and `dp_foreign_range` a rank's step runs (vaeb_hip.hip), on a host-only
+`dp_opt_range` and `dp_foreign_range` a rank's step runs (dp_buckets.inc), on a host-only
 context: no GPU call, so this is a CPU test of the shipped .so.  The plan splits the
 reference's simultaneous Adagrad (VAEB.py:426-444) over ranks; checked here:
 * it equals the Python mirror `vaeb_amd.dp.shard_plan` (which the gloo world-2 optimizer test

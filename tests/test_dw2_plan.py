@@ -59,6 +59,24 @@ def test_the_narrowest_fitting_width_is_taken():
     assert big["paired"] and big["workers"] == 33 * 128
 
 
+VEC_CASES = [
+    # D, H, Z, B, decoder -> width, paired, workers, free_cus
+    ("D_not_mult_of_4", 786, 500, 20, 132, _lib.DEC_BERNOULLI, 32, True, 200, 112),
+    ("H_not_mult_of_4", 784, 498, 20, 132, _lib.DEC_BERNOULLI, 32, True, 200, 112),
+    ("scalar_path_still_takes_48", 786, 500, 20, 100, _lib.DEC_BERNOULLI, 48, False, 136, 144),
+    ("gaussian", 784, 500, 20, 132, _lib.DEC_GAUSSIAN, 32, True, 392, 112),
+]
+
+
+@pytest.mark.parametrize("name,D,H,Z,Bc,dec,width,paired,workers,free", VEC_CASES, ids=[c[0] for c in VEC_CASES])
+def test_64_wide_tiles_only_with_16_byte_accesses(name, D, H, Z, Bc, dec, width, paired, workers, free):
+    """64-wide tiles are a candidate only where the dW2 group may use 16-byte accesses (the one
+    predicate the weight-gradient launches use: H, D and the group's arena offsets % 4 == 0).
+    At B = 132 the 48-wide tiles do not fit, so without them the plan is the paired form."""
+    pl = _lib.dw2_plan(D, H, Z, Bc, decoder=dec)
+    assert (pl["width"], bool(pl["paired"]), pl["workers"], pl["free_cus"]) == (width, paired, workers, free)
+
+
 def test_bias_row_placement():
     last = _lib.dw2_plan(784, 319, 20, B)["ranges"][-1]
     assert last[:2] == (256, 320)            # rows 256..318 and the bias row 319 in one tile

@@ -137,7 +137,7 @@ def test_vaeb_optimizer_plugin_binds_the_engine_rule():
 
 @pytest.mark.parametrize("continuous,overlap", [(False, "0"), (True, "1"), (False, "1")])
 def test_sharded_dp_optimizer_world1_is_bitwise_the_replicated_one(continuous, overlap, monkeypatch):
-    """the sharded DP optimizer (vaeb_hip.hip dp_reduce_update: reduce-scatter of
+    """the sharded DP optimizer (dp_buckets.inc dp_reduce_update: reduce-scatter of
     each arena run's 64-aligned shards + all-reduce of the remainders and the SGVB slot, this
     rank's shard of prior + Adagrad, all-gather of theta' shards) forced at world 1 equals the
     replicated DP path (all-reduce, Adagrad over the whole arena) bit for bit: ELBO, theta and

@@ -2,7 +2,7 @@
 
 SURVEY §8(e): the step shards by rows, so the reduced gradient is a sum over ranks and the
 reference's simultaneous Adagrad (/root/reference/VAEB.py:426-444, the -1/2 sum theta^2 prior of
-:386-390) is elementwise.  The library's sharded form (vaeb_hip.hip dp_reduce_update) reduce-
+:386-390) is elementwise.  The library's sharded form (dp_buckets.inc dp_reduce_update) reduce-
 scatters each arena run, updates this rank's 1/W shard plus the replicated remainders, all-gathers
 theta' and (bf16 engine) rewrites the shadow of the shards other ranks updated
 (step_bf16.hpp shadow_runs_kernel).  RCCL needs one GPU per rank, so the collectives are
@@ -61,7 +61,7 @@ def run_rank(ctx, world, rank, buckets, gsum, theta0, acc0, thg, n_w):
 
 def gathered(parts, plans):
     """What the all-gather (theta') / dp_gather_acc (Adagrad state) assemble: shard k of each run
-    from rank k, the replicated remainder from rank 0 (vaeb_hip.hip dp_reduce_update,
+    from rank k, the replicated remainder from rank 0 (dp_buckets.inc dp_reduce_update,
     dp_gather_acc)."""
     out = np.full_like(parts[0], np.nan)
     for plan in plans:

@@ -1,4 +1,4 @@
-"""The deferred dW2 (| dW6) tiling (vaeb_hip.hip w2_plan, latent.hpp enc_latent16_w2_kernel): one
+"""The deferred dW2 (| dW6) tiling (engine_f32.inc w2_plan, latent.hpp enc_latent16_w2_kernel): one
 tile worker per workgroup at the planned width, dispatched ahead of the encoder rows, against
 the in-step dW2 (VAEB_DW2_DEFER=0, 32-wide tiles in the dhd launch) and the paired 32-wide form
 (VAEB_DW2_PAIRED=1): bit for bit, because no form changes the order in which an output element's

@@ -1,6 +1,6 @@
 """The evaluation-only forward of the fp32 engine, row by row against the float64 oracle.
 
-Evaluation chunks never take the folded training kernels (vaeb_hip.hip folded_latent), so
+Evaluation chunks never take the folded training kernels (engine_f32.inc folded_latent), so
 vaeb_validate, vaeb_validate_resident, vaeb_reconstruct*, vaeb_decode and vaeb_encode run PEnc
 (big-K), heads_dechid_kernel<1 | 2> (Z <= 32) or PHeads + PDecHid (Z > 32), PDecOut in MODE_EVAL /
 MODE_RECON and elbo_kernel -- kernels a training step with Z <= 32 never launches.  Here they are

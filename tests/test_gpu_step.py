@@ -64,6 +64,34 @@ CASES = [
     # atomic latent hand-offs (fan-in <= 16) with two fx slots per thread (Z > 16)
     ("latent24_atomic_L2", dict(D=784, H=128, Z=24, L=2), 100),
     ("latent28_atomic_LA", dict(D=200, H=96, Z=28, estimator="LA", L=2), 50),
+    # the Gaussian decoder's folded decout at 16 < Z <= 32 (5 / 8 latent quads per thread): behind
+    # the slab encoder (H = 272: fan-in 17), behind the counted atomics, and with H % 4 != 0
+    ("gauss_latent20_slab", dict(D=48, H=272, Z=20, continuous=True), 20),
+    ("gauss_latent28_atomic", dict(D=40, H=32, Z=28, continuous=True), 20),
+    ("gauss_latent18_odd_H", dict(D=45, H=30, Z=18, continuous=True), 17),
+    # the remaining decoder arms behind the counted atomics (H <= 256): latent quads per thread
+    # 1 / 2 / 4 / 5 / 8 (Z <= 4 / 8 / 16 / 20 / 32) x 16-byte W1 loads (H % 4 == 0) or scalar ones;
+    # D = 530: the dhd launch's K > 512 main loop with scalar loads (D % 4 != 0)
+    ("bern_latent4_atomic", dict(D=40, H=32, Z=4), 20),
+    ("bern_latent12_odd_H_deep", dict(D=530, H=30, Z=12), 17),
+    ("bern_latent18_odd_H_deep", dict(D=530, H=30, Z=18), 17),
+    ("bern_latent28_odd_H", dict(D=45, H=30, Z=28), 17),
+    ("gauss_latent2_odd_H", dict(D=45, H=30, Z=2, continuous=True), 17),
+    # (D = 224: > 1e4 parameters, so that check_theta's 1e-4 fraction leaves room for one element with
+    # |g| ~ 1e-6 to flip, as its docstring allows; at D = 40 one flip of 4572 elements is 2.2e-4)
+    ("gauss_latent6_atomic", dict(D=224, H=32, Z=6, continuous=True), 20),
+    ("gauss_latent12_odd_H", dict(D=45, H=30, Z=12, continuous=True), 17),
+    ("gauss_latent28_odd_H", dict(D=45, H=30, Z=28, continuous=True), 17),
+    # ... and behind the slab encoder (H = 272 / 274: fan-in 17, one 16-row block more than B = 16)
+    ("gauss_latent2_slab_odd_H", dict(D=45, H=274, Z=2, continuous=True), 20),
+    ("gauss_latent6_slab", dict(D=40, H=272, Z=6, continuous=True), 20),
+    ("gauss_latent12_slab_odd_H", dict(D=45, H=274, Z=12, continuous=True), 20),
+    ("gauss_latent12_slab", dict(D=40, H=272, Z=12, continuous=True), 20),
+    ("gauss_latent18_slab_odd_H", dict(D=45, H=274, Z=18, continuous=True), 20),
+    ("gauss_latent28_slab_odd_H", dict(D=45, H=274, Z=28, continuous=True), 20),
+    ("gauss_latent28_slab", dict(D=40, H=272, Z=28, continuous=True), 20),
+    ("bern_latent12_slab_odd_H", dict(D=45, H=274, Z=12), 20),
+    ("bern_latent28_slab_odd_H", dict(D=45, H=274, Z=28), 20),
 ]
 
 
@@ -208,9 +236,32 @@ def test_reconstruct_sampled_philox():
     assert np.all((y1 > 0) & (y1 < 1))
 
 
-def test_fv_literal_step():
-    cfg = O.Config(D=560, H=200, Z=2, continuous=True, estimator="FV")
-    B = 100
+# the literal-FV encoder (the FV stream in its extra grid rows): the K > 512 main loop, and the
+# K <= 512 one at one / two latent column tiles (Z <= 16 / > 16)
+FV_CASES = [
+    ("frey2", dict(D=560, H=200, Z=2), 100),
+    ("shallow_latent2", dict(D=48, H=32, Z=2), 32),
+    ("shallow_latent20", dict(D=48, H=32, Z=20), 32),
+    # H > 512: 17 two-tile column blocks, so the ticketed hand-off and the decoder behind it
+    # (AT 0), at every latent-quad count, with 16-byte (H = 544) and scalar (H = 546) W1 loads
+    ("ticket_gauss_latent2_odd_H", dict(D=48, H=546, Z=2), 32),
+    ("ticket_gauss_latent6", dict(D=48, H=544, Z=6), 32),
+    ("ticket_gauss_latent12_odd_H", dict(D=48, H=546, Z=12), 32),
+    ("ticket_gauss_latent12_deep", dict(D=530, H=544, Z=12), 32),
+    ("ticket_gauss_latent18_odd_H", dict(D=48, H=546, Z=18), 32),
+    ("ticket_gauss_latent28_odd_H_deep", dict(D=530, H=546, Z=28), 32),
+    ("ticket_gauss_latent28", dict(D=48, H=544, Z=28), 32),
+    ("ticket_bern_latent6", dict(D=48, H=544, Z=6, continuous=False), 32),
+    ("ticket_bern_latent12_odd_H", dict(D=48, H=546, Z=12, continuous=False), 32),
+    ("ticket_bern_latent12", dict(D=48, H=544, Z=12, continuous=False), 32),
+    ("ticket_bern_latent18_odd_H", dict(D=48, H=546, Z=18, continuous=False), 32),
+    ("ticket_bern_latent28_odd_H", dict(D=48, H=546, Z=28, continuous=False), 32),
+]
+
+
+@pytest.mark.parametrize("name,kw,B", FV_CASES, ids=[c[0] for c in FV_CASES])
+def test_fv_literal_step(name, kw, B):
+    cfg = O.Config(**{"continuous": True, "estimator": "FV", **kw})
     x = data_for(cfg, 1500)
     theta = O.init_params(cfg)
     rng = np.random.default_rng(4)
@@ -467,8 +518,18 @@ def test_atomic_and_slab_handoffs_agree(kw, monkeypatch):
     assert max(frac.values()) <= 2e-3, frac
 
 
-@pytest.mark.parametrize("kw", [dict(D=784, H=500, Z=20), dict(D=560, H=200, Z=2, continuous=True)],
-                         ids=["mnist20", "frey2"])
+# the deferred dW2 behind the slab encoder at 48 scalar / 64 wide tiles, and behind the atomic
+# encoder (H = 240: forward fan-in 15, backward fan-in 30 with L = 2; B = 256 leaves 16 CUs
+# free) at every tiling: D = 126 / 128 one 32-wide tile per workgroup (scalar / 16-byte), 190 / 192
+# 48 wide, 256 64 wide, 194 / 260 two 32-wide tiles per workgroup; Z = 4 / 20: one / two latent tiles
+DEFER_CASES = [("mnist20", dict(D=784, H=500, Z=20)), ("frey2", dict(D=560, H=200, Z=2, continuous=True)),
+               ("slab_48_scalar_latent4", dict(D=786, H=500, Z=4)), ("slab_48_scalar_latent20", dict(D=786, H=500, Z=20)),
+               ("slab_64_latent4", dict(D=784, H=500, Z=4, B=132))]
+DEFER_CASES += [(f"atomic_D{D}_latent{Z}", dict(D=D, H=240, Z=Z, L=2, B=256))
+                for Z, Ds in ((4, (128, 190, 192, 194, 256, 260)), (20, (126, 190, 192, 194, 256, 260))) for D in Ds]
+
+
+@pytest.mark.parametrize("kw", [c[1] for c in DEFER_CASES], ids=[c[0] for c in DEFER_CASES])
 def test_deferred_dw2_is_bitwise_the_same_step(kw, monkeypatch, tmp_path):
     """The deferred dW2 (step t's dW2 | dW6 + Adagrad in step t+1's encoder launch, the last
     one flushed when the host reads the state) runs the same tiles with the same K split as
@@ -476,13 +537,15 @@ def test_deferred_dw2_is_bitwise_the_same_step(kw, monkeypatch, tmp_path):
     host reads, a validation and a checkpoint round trip between calls, the synchronous
     update() among them, and graph replay as well as eager steps."""
     from vaeb_amd import _lib
+    kw = dict(kw)
+    B = kw.pop("B", 100)
     cfg = O.Config(**kw)
-    x = data_for(cfg, 800)
+    x = data_for(cfg, 8 * B)
     res = {}
     for defer in ("1", "0"):
         for use_graph in (True, False):
             monkeypatch.setenv("VAEB_DW2_DEFER", defer)
-            ctx = _lib.Context(cfg.D, cfg.H, cfg.Z, 100, decoder=int(cfg.continuous), max_eval_rows=200,
+            ctx = _lib.Context(cfg.D, cfg.H, cfg.Z, B, L=cfg.L, decoder=int(cfg.continuous), max_eval_rows=200,
                                use_graph=use_graph)
             ctx.set_data(x)
             ctx.set_params(O.flatten(O.init_params(cfg)))

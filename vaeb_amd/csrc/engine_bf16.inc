@@ -187,11 +187,13 @@ int bf_alloc(vaeb_ctx* c) {
     b.s26 = b.s1 + (int64_t)Z * H;
     b.S = b.s26 + (int64_t)H * b.Dn;
     bf::ShadowMap& m = b.smap;
-    m.offW3 = c->off[0]; m.offW4 = c->off[1]; m.offW5 = c->off[2]; m.offW1 = c->off[3]; m.offW2 = c->off[4];
-    m.offW6 = gs ? c->off[5] : -1;
+    const ArenaSlots& sl = c->sl;
+    m.offW3 = c->off[sl.W3]; m.offW4 = c->off[sl.W4]; m.offW5 = c->off[sl.W5]; m.offW1 = c->off[sl.W1];
+    m.offW2 = c->off[sl.W2];
+    m.offW6 = gs ? c->off[sl.W6] : -1;
     m.s3 = b.s3; m.s45 = b.s45; m.s1 = b.s1; m.s26 = b.s26;
     m.D = D; m.H = H; m.Z = Z;
-    m.nweights = c->off[gs ? 6 : 5];
+    m.nweights = c->off[sl.b3];   // the biases follow the weight matrices
     const int64_t R = c->cap, RL = (int64_t)c->cap * L;
     const int B = g.B;
     b.ks_heads = bf_split(B, 2 * Z, H);
@@ -312,12 +314,12 @@ int bf_forward(vaeb_ctx* c, int par, const BfFwd& f, Prof& pr) {
     const bf16_t* sh = b.shadow2[par];
     const float* t = c->theta2[par];
     const bool gs = gaussian(c);
-    const int bo = gs ? 6 : 5;
-    const float *b3 = t + c->off[bo], *b4 = t + c->off[bo + 1], *b5 = t + c->off[bo + 2], *b1 = t + c->off[bo + 3],
-                *b2 = t + c->off[bo + 4], *b6 = gs ? t + c->off[bo + 5] : nullptr;
+    const ArenaSlots& as = c->sl;
+    const float *b3 = t + c->off[as.b3], *b4 = t + c->off[as.b4], *b5 = t + c->off[as.b5], *b1 = t + c->off[as.b1],
+                *b2 = t + c->off[as.b2], *b6 = gs ? t + c->off[as.b6] : nullptr;
     const int64_t xbytes = (int64_t)M * D * 2;
     // enc: h = tanh(X W3 + b3)
-    pr.mark(18);
+    pr.mark(K_BF_ENC);
     // (256 x 128 tiles with two blocks per CU, as decout: +21 us per step, removed in round 3)
     REP(pr) if (int rc = bf_gemm<bf::KC, bf::KO>(s, f.x, D, xbytes, sh + b.s3, H, (int64_t)D * H * 2, M, H, D, 1,
                                                   bf::EpiBiasAct{b3, 1, M, H, b.h, H}, f.xb)) return rc;
@@ -332,12 +334,12 @@ int bf_forward(vaeb_ctx* c, int par, const BfFwd& f, Prof& pr) {
         eh.eps_mode = c->eps_mode == VAEB_EPS_HOST ? 1 : 0; eh.seed = c->seed; eh.step = c->step; eh.domain = f.domain;
         eh.eps_in = f.eps_in; eh.eps_in_ld = f.eps_in_ld;
         eh.rows = f.xb; eh.row_base_mul = f.row_base_mul; eh.row_base_add = f.row_base_add;
-        pr.mark(19);
+        pr.mark(K_BF_HEADS);
         REP(pr) if (int rc = bf_thin<bf::KO, 64>(s, ta, dim3(cdiv(M, 64), Z / 64), eh)) return rc;
     } else {
     // heads: [mu | lv] split-K slabs
     const int ksh = bf_slices(H, b.ks_heads);
-    pr.mark(19);
+    pr.mark(K_BF_HEADS);
     REP(pr) if (int rc = bf_gemm<bf::KC, bf::KO>(s, b.h, H, (int64_t)M * H * 2, sh + b.s45, 2 * Z,
                                                   (int64_t)H * 2 * Z * 2, M, 2 * Z, H, b.ks_heads,
                                                   bf::EpiF32{b.ml_slab, 2 * Z, M, 2 * Z, (int64_t)M * 2 * Z})) return rc;
@@ -350,7 +352,7 @@ int bf_forward(vaeb_ctx* c, int par, const BfFwd& f, Prof& pr) {
     la.eps_mode = c->eps_mode == VAEB_EPS_HOST ? 1 : 0; la.seed = c->seed; la.step = c->step; la.domain = f.domain;
     la.eps_in = f.eps_in; la.eps_in_ld = f.eps_in_ld;
     la.rows = f.xb; la.row_base_mul = f.row_base_mul; la.row_base_add = f.row_base_add;
-    pr.mark(20);
+    pr.mark(K_BF_LATENT);
     if (bf_lat4(c, la)) REP(pr) hipLaunchKernelGGL(bf::latent_fwd_v4_kernel, dim3(cdiv(M, 8)), dim3(256), 0, s, la);
     else REP(pr) hipLaunchKernelGGL(bf::latent_fwd_kernel, dim3(cdiv(M, 4)), dim3(256), 0, s, la);
     CHECK_LAUNCH();
@@ -358,11 +360,11 @@ int bf_forward(vaeb_ctx* c, int par, const BfFwd& f, Prof& pr) {
     const float lsc = (g.objective == VAEB_OBJ_MEAN_MAP) ? 1.0f / (float)g.B_global : 1.0f;
     // dechid: hd = tanh(z W1 + b1) on 256 x 128 tiles, two blocks per CU (K = Z is short: the
     // second block's epilogue overlaps the first's; 743.3 -> 739.8 us per step in round 5)
-    pr.mark(21);
+    pr.mark(K_BF_DECHID);
     REP(pr) if (int rc = bf_gemm_2b<bf::KC, bf::KO>(s, b.z, Z, (int64_t)LM * Z * 2, sh + b.s1, H, (int64_t)Z * H * 2,
                                                      LM, H, Z, bf::EpiBiasAct{b1, 1, LM, H, b.hd, H})) return rc;
     // decout: log p(x|z) partials, dA2 (| dA6), bias partials, y
-    pr.mark(22);
+    pr.mark(K_BF_DECOUT);
     const int nlp = cdiv(Dn, 64);
     // (dA is stored with the backward's loss scale: the fp16 mean objective, h16_scale)
     const float sl = lsc / (float)L * (f.train ? h16_scale(c) : 1.f);
@@ -452,7 +454,7 @@ int bf_train_step(vaeb_ctx* c, int par, bool prof, int direct) {
 
     const bool dp = c->comm != nullptr;
     const bf::Opt opt = bf_opt(c, par, !dp, dp || g.keep_grads != 0);
-    const int bo = gs ? 6 : 5;
+    const ArenaSlots& sl = c->sl;
     // DP: replicated Adagrad (+ bf16 shadows) over an all-reduced gradient bucket
     bf::Opt dopt = bf_opt(c, par, true, false);
     dopt.shadow_out = b.shadow2[par ^ 1];
@@ -467,7 +469,7 @@ int bf_train_step(vaeb_ctx* c, int par, bool prof, int direct) {
     const bf::EpiDTanh e_dhd{b.hd, H, LM, H, b.dA1, H, b.cp1};
     bf::Opt o26 = opt;
     o26.shadow_out = b.shadow2[par ^ 1] + b.s26;
-    bf::EpiAdagrad e_w26{cmap(gs ? 2 : 0, 0, c->off[4], gs ? c->off[5] : 0, D, D), o26, H, Dn};
+    bf::EpiAdagrad e_w26{cmap(gs ? 2 : 0, 0, c->off[sl.W2], gs ? c->off[sl.W6] : 0, D, D), o26, H, Dn};
     e_w26.vec = adagrad_vec(e_w26);
     // fork (not profiled, not DP): dhd on the whole chip first; then the weight gradients
     // off the critical path -- dW1, dW2 (| dW6) on 128 256 x 256 tiles, and (once [dMu | dLv]
@@ -481,7 +483,7 @@ int bf_train_step(vaeb_ctx* c, int par, bool prof, int direct) {
     const bool dzf = fork && c->bf_dzfuse && c->bf_dtt && H % 8 == 0 && Z <= 128 && Z % 16 == 0 && use8<bf::KC, bf::KC>();
     const hipStream_t sw = fork ? c->s3 : s;   // the off-path weight gradients' stream
     if (fork) {
-        pr.mark(23);
+        pr.mark(K_BF_DHD);
         if (dzf) {
             // ... and dZ as split-K slabs from the dA1 tile in LDS (EpiDTanhTDz, VAEB_BF_DZFUSE)
             const bf::EpiDTanhTDz e{{b.hd, H, LM, H, b.dA1, H, b.cp1}, sh + b.s1, Z, H, b.dz_slab, (int64_t)LM * Z};
@@ -499,14 +501,14 @@ int bf_train_step(vaeb_ctx* c, int par, bool prof, int direct) {
     } else {
         const bf::GemmArgs gw = bf_args256(b.hd, H, (int64_t)LM * H * 2, b.dA, Dn, (int64_t)LM * Dn * 2, H, Dn, LM);
         const bf::GemmArgs gd = bf_args256(b.dA, Dn, (int64_t)LM * Dn * 2, sh + b.s26, Dn, (int64_t)H * Dn * 2, LM, H, Dn);
-        pr.mark(41);
+        pr.mark(K_BF_DHD_DW26);
         REP(pr) if (int rc = bf_gemm2<bf::KO, bf::KO, bf::EpiAdagrad, bf::KC, bf::KC, bf::EpiDTanh>(s, gw, e_w26, gd, e_dhd))
             return rc;
     }
     if (dp && !fork) if (int rc = dp_bucket_a(c, pr, dopt.th_out, dp_opt, dp_fix)) return rc;
     // dz slabs = dA1 W1^T  (thin: dz + latent backward in one launch, after dW1's fork below)
     const int ksz = bf_slices(H, b.ks_dz);
-    if (!b.thin_z && !dzf) pr.mark(25);
+    if (!b.thin_z && !dzf) pr.mark(K_BF_DZ);
     if (!b.thin_z && !dzf)
     REP(pr) if (int rc = bf_gemm<bf::KC, bf::KC>(s, b.dA1, H, (int64_t)LM * H * 2, sh + b.s1, H, (int64_t)Z * H * 2,
                                                   LM, Z, H, b.ks_dz,
@@ -531,15 +533,15 @@ int bf_train_step(vaeb_ctx* c, int par, bool prof, int direct) {
         }
         // dW1 = z^T dA1 (split-K slabs) -> optimizer
         const int ks1 = bf_slices(LM, b.ks_w1);
-        pr.mark(26);
+        pr.mark(K_BF_DW1);
         REP(pr) if (int rc = bf_gemm<bf::KO, bf::KO>(sw, b.z, Z, (int64_t)LM * Z * 2, b.dA1, H, (int64_t)LM * H * 2,
                                                       Z, H, LM, b.ks_w1,
                                                       bf::EpiF32{b.w_slab, H, Z, H, (int64_t)Z * H})) return rc;
         bf::WReduceArgs w{};
         w.slab = b.w_slab; w.nslab = ks1; w.M = Z; w.N = H;
-        w.map = cmap(0, 0, c->off[3], 0, H, 0);
+        w.map = cmap(0, 0, c->off[sl.W1], 0, H, 0);
         w.opt = opt; w.opt.shadow_out = b.shadow2[par ^ 1] + b.s1;
-        pr.mark(27);
+        pr.mark(K_BF_DW1_OPT);
         REP(pr) hipLaunchKernelGGL(bf::wreduce_opt_kernel, dim3(std::min(1024, cdiv((int64_t)Z * H, 256))), dim3(256),
                                    0, sw, w);
         CHECK_LAUNCH();
@@ -560,7 +562,7 @@ int bf_train_step(vaeb_ctx* c, int par, bool prof, int direct) {
     la.sc = ((g.objective == VAEB_OBJ_MEAN_MAP) ? 1.0f / (float)g.B_global : 1.0f) * h16_scale(c);
     la.mu = b.mu; la.lv = b.lv; la.eps = b.eps;
     la.dz_slab = b.dz_slab; la.ndz = ksz; la.dmulv = b.dml; la.colpart = b.cp45;
-    pr.mark(28);
+    pr.mark(K_BF_LATENT_BWD);
     if (dzf) {
         // the dhd blocks stored dZ as cdiv(H, 256) split-K slabs: the latent backward sums them
         la.ndz = cdiv(H, 256);
@@ -586,7 +588,7 @@ int bf_train_step(vaeb_ctx* c, int par, bool prof, int direct) {
         HIP_TRY(hipStreamWaitEvent(c->s3, c->fk_ev[2], 0));
     }
     // dh: dA3 = ([dMu | dLv] [W4 | W5]^T) (1 - h^2)
-    pr.mark(29);
+    pr.mark(K_BF_DH);
     if (c->bf_dtt && H % 8 == 0) {
         // the transposed product dA3^T = [W4 | W5] [dMu | dLv]^T (EpiDTanhT)
         REP(pr) if (int rc = bf_gemm<bf::KC, bf::KC>(s, sh + b.s45, 2 * Z, (int64_t)H * 2 * Z * 2, b.dml, 2 * Z,
@@ -600,15 +602,15 @@ int bf_train_step(vaeb_ctx* c, int par, bool prof, int direct) {
     // dW4 | dW5 = h^T [dMu | dLv] (split-K slabs) -> optimizer
     {
         const int ks45 = bf_slices(M, b.ks_w45);
-        pr.mark(30);
+        pr.mark(K_BF_DW45);
         REP(pr) if (int rc = bf_gemm<bf::KO, bf::KO>(sw, b.h, H, (int64_t)M * H * 2, b.dml, 2 * Z, (int64_t)M * 2 * Z * 2,
                                                       H, 2 * Z, M, b.ks_w45,
                                                       bf::EpiF32{b.w_slab, 2 * Z, H, 2 * Z, (int64_t)H * 2 * Z})) return rc;
         bf::WReduceArgs w{};
         w.slab = b.w_slab; w.nslab = ks45; w.M = H; w.N = 2 * Z;
-        w.map = cmap(1, Z, c->off[1], c->off[2], Z, Z);
+        w.map = cmap(1, Z, c->off[sl.W4], c->off[sl.W5], Z, Z);
         w.opt = opt; w.opt.shadow_out = b.shadow2[par ^ 1] + b.s45;
-        pr.mark(31);
+        pr.mark(K_BF_DW45_OPT);
         REP(pr) hipLaunchKernelGGL(bf::wreduce_opt_kernel, dim3(std::min(1024, cdiv((int64_t)H * 2 * Z, 256))),
                                    dim3(256), 0, sw, w);
         CHECK_LAUNCH();
@@ -617,9 +619,9 @@ int bf_train_step(vaeb_ctx* c, int par, bool prof, int direct) {
     {
         bf::Opt o = opt;
         o.shadow_out = b.shadow2[par ^ 1] + b.s3;
-        bf::EpiAdagrad e{cmap(0, 0, c->off[0], 0, H, 0), o, D, H};
+        bf::EpiAdagrad e{cmap(0, 0, c->off[sl.W3], 0, H, 0), o, D, H};
         e.vec = adagrad_vec(e);
-        pr.mark(32);
+        pr.mark(K_BF_DW3);
         if (fork) {
             // beside the forked dW2 (128 256 x 256 tiles) each product holds half the chip:
             // 256 x 256 tiles here too (ping-pong, the better tile) instead of 256 x 128
@@ -639,10 +641,10 @@ int bf_train_step(vaeb_ctx* c, int par, bool prof, int direct) {
         const bool dtt = c->bf_dtt && H % 8 == 0;
         const int nrb3 = dtt ? bf_rowblocks_t(M, H) : nrbM;
         const int nrb1 = dzf ? cdiv(LM, 256) * 4 : (fork && dtt) ? bf_rowblocks_t(LM, H) : nrbL;
-        ba.seg[0] = bf::BiasSeg{b.cp3, nrb3, H, cmap(0, 0, c->off[bo + 0], 0, 0, 0)};
-        ba.seg[1] = bf::BiasSeg{b.cp45, cdiv(M, bf::kLbRows), 2 * Z, cmap(1, Z, c->off[bo + 1], c->off[bo + 2], 0, 0)};
-        ba.seg[2] = bf::BiasSeg{b.cp1, nrb1, H, cmap(0, 0, c->off[bo + 3], 0, 0, 0)};
-        ba.seg[3] = bf::BiasSeg{b.cp26, nrbL, Dn, cmap(gs ? 2 : 0, 0, c->off[bo + 4], gs ? c->off[bo + 5] : 0, 0, 0)};
+        ba.seg[0] = bf::BiasSeg{b.cp3, nrb3, H, cmap(0, 0, c->off[sl.b3], 0, 0, 0)};
+        ba.seg[1] = bf::BiasSeg{b.cp45, cdiv(M, bf::kLbRows), 2 * Z, cmap(1, Z, c->off[sl.b4], c->off[sl.b5], 0, 0)};
+        ba.seg[2] = bf::BiasSeg{b.cp1, nrb1, H, cmap(0, 0, c->off[sl.b1], 0, 0, 0)};
+        ba.seg[3] = bf::BiasSeg{b.cp26, nrbL, Dn, cmap(gs ? 2 : 0, 0, c->off[sl.b2], gs ? c->off[sl.b6] : 0, 0, 0)};
         ba.nseg = 4;
         ba.total = H + 2 * Z + H + Dn;
         int nbias = 0;
@@ -653,7 +655,7 @@ int bf_train_step(vaeb_ctx* c, int par, bool prof, int direct) {
         if (dp) { e.dp_slot = c->grad + c->P; e.elbo_out = nullptr; e.cursor = nullptr; e.step = nullptr; }
         ba.elbo = e;
         ba.elbo_parts = b.elbo_parts; ba.n_elbo_parts = bf::kElboBlocks;
-        pr.mark(33);
+        pr.mark(K_BF_BIAS_ELBO);
         if (fork) {
             // the ELBO's stage-1 partials on the main stream after dW3: the second stream's tail,
             // not the main chain, ends the step once dz is in dhd (round 5: -2 us against them on
@@ -673,13 +675,13 @@ int bf_train_step(vaeb_ctx* c, int par, bool prof, int direct) {
             HIP_TRY(hipEventRecord(c->fk_ev[1], c->s3));
             HIP_TRY(hipStreamWaitEvent(s, c->fk_ev[1], 0));
         }
-        if (dp) if (int rc = dp_bucket_b(c, pr, 34, dopt.th_out, dp_opt, dp_fix)) return rc;
+        if (dp) if (int rc = dp_bucket_b(c, pr, K_BF_ADAGRAD_DP, dopt.th_out, dp_opt, dp_fix)) return rc;
     }
     if (fork && !dp) {
         HIP_TRY(hipEventRecord(c->fk_ev[1], c->s3));
         HIP_TRY(hipStreamWaitEvent(s, c->fk_ev[1], 0));
     }
-    pr.mark(-1);
+    pr.mark(K_END);
     c->prof_n = pr.k;
     return 0;
 }

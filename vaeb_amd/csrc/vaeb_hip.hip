@@ -85,23 +85,48 @@ constexpr int kGraphSteps = 32;  // the longest replayed graph
 constexpr int kMaxProfKernels = 24;
 constexpr int kDbgWG = 1024;      // diagnostics: stamp slots per launch (workgroups)
 
+// Profile ids (Prof::mark, vaeb_profile_steps) and their names (vaeb_kernel_name), in the same
+// order: profiles and bench.py rely on the names, callers of vaeb_profile_steps on the values.
+enum KernelId : int {
+    K_END = -1,   // closes the last bracket
+    K_P1_ENC, K_P2_HEADS, K_P3_DECHID, K_P4_DECOUT, K_P5_DHD_W2, K_P6_DZ,
+    K_P7_DH, K_P8_WGRAD_W3W45, K_ALLREDUCE, K_ADAGRAD, K_FV_UPDATE, K_ELBO,
+    K_P23_HEADS_DECHID, K_P67_DZ_DH_W1, K_P8_WGRAD_W2, K_P8_WGRAD_W1,
+    K_P1_ENC_LATENT, K_P4_DECOUT_Z,
+    K_BF_ENC, K_BF_HEADS, K_BF_LATENT, K_BF_DECHID, K_BF_DECOUT, K_BF_DHD, K_BF_DW26,
+    K_BF_DZ, K_BF_DW1, K_BF_DW1_OPT, K_BF_LATENT_BWD, K_BF_DH, K_BF_DW45, K_BF_DW45_OPT,
+    K_BF_DW3, K_BF_BIAS_ELBO, K_BF_ADAGRAD_DP,
+    K_UNUSED35, K_UNUSED36, K_FVS_SAMPLE, K_FVS_UPDATE,
+    K_P5_DHD_DZ_W2, K_P8_WGRAD_W3W45W1,
+    K_BF_DHD_DW26,
+    K_P1_ENC_LATENT_W2, K_P5_DHD_DZ,
+    kNumKernelIds
+};
 const char* kKernelNames[] = {"p1_enc", "p2_heads", "p3_dechid", "p4_decout", "p5_dhd_w2", "p6_dz",
                               "p7_dh", "p8_wgrad_w3w45", "allreduce", "adagrad", "fv_update", "elbo",
                               "p23_heads_dechid", "p67_dz_dh_w1", "p8_wgrad_w2", "p8_wgrad_w1",
                               "p1_enc_latent", "p4_decout_z",
-                              // bf16 engine (step_bf16.hpp), ids 18..34
+                              // bf16 engine (step_bf16.hpp)
                               "bf_enc", "bf_heads", "bf_latent", "bf_dechid", "bf_decout", "bf_dhd", "bf_dW26",
                               "bf_dz", "bf_dW1", "bf_dW1_opt", "bf_latent_bwd", "bf_dh", "bf_dW45", "bf_dW45_opt",
                               "bf_dW3", "bf_bias_elbo", "bf_adagrad_dp",
-                              // weight-sampling full-variational extension, ids 35..38
+                              // weight-sampling full-variational extension (two retired slots first)
                               "unused35", "unused36", "fvs_sample", "fvs_update",
-                              // folded latent backward (latent_bwd.hpp), ids 39..40
+                              // folded latent backward (latent_bwd.hpp)
                               "p5_dhd_dz_w2", "p8_wgrad_w3w45w1",
-                              // bf16 engine: dhd and dW2 (| dW6) in one grid, id 41
+                              // bf16 engine: dhd and dW2 (| dW6) in one grid
                               "bf_dhd_dW26",
                               // deferred dW2 (round 4): the encoder launch carries the previous
-                              // step's dW2 tiles; the dhd launch has none, ids 42..43
+                              // step's dW2 tiles; the dhd launch has none
                               "p1_enc_latent_w2", "p5_dhd_dz"};
+static_assert(kNumKernelIds == sizeof(kKernelNames) / sizeof(kKernelNames[0]), "one name per KernelId");
+static_assert(K_UNUSED35 == 35 && K_P5_DHD_DZ == 43, "profile ids are part of the ABI");
+
+// Where each parameter sits in c->off (set_arena_layout): the reference order
+// W3 W4 W5 W1 W2 [W6] b3 b4 b5 b1 b2 [b6]; W6 / b6 are -1 with the Bernoulli decoder.
+struct ArenaSlots {
+    int W3, W4, W5, W1, W2, W6, b3, b4, b5, b1, b2, b6;
+};
 
 }  // namespace
 
@@ -111,6 +136,7 @@ struct vaeb_ctx {
     int64_t P = 0;
     int nparams = 0;
     int64_t off[12] = {};   // arena offsets, reference order
+    ArenaSlots sl{};        // off's index of each parameter
     // arenas
     float* theta2[2] = {nullptr, nullptr};   // ping-pong parameter arenas
     int par = 0;                              // arena holding the current parameters
@@ -207,149 +233,22 @@ namespace {
 bool gaussian(const vaeb_ctx* c) { return c->c.decoder == VAEB_DEC_GAUSSIAN; }
 
 // The parameter arena in reference order W3 W4 W5 W1 W2 [W6] b3 b4 b5 b1 b2 [b6]
-// (VAEB.py:74-104): c->off, c->nparams, c->P from the config alone (no device call).
+// (VAEB.py:74-104): c->off, c->sl, c->nparams, c->P from the config alone (no device call).
 void set_arena_layout(vaeb_ctx* c) {
     const int64_t D = c->c.D, H = c->c.H, Z = c->c.Z;
+    const bool gs = gaussian(c);
     std::vector<int64_t> sz = {D * H, H * Z, H * Z, Z * H, H * D};
-    if (gaussian(c)) sz.push_back(H * D);
+    if (gs) sz.push_back(H * D);
     sz.insert(sz.end(), {H, Z, Z, H, D});
-    if (gaussian(c)) sz.push_back(D);
+    if (gs) sz.push_back(D);
     c->nparams = (int)sz.size();
     int64_t o = 0;
     for (int i = 0; i < c->nparams; ++i) { c->off[i] = o; o += sz[i]; }
     c->P = o;
-}
-
-uint64_t* next_dbg(vaeb_ctx* c) { return c->dbg ? c->dbg + (size_t)(c->dbg_slot++) * kDbgWG * 8 : nullptr; }
-
-int order_hook(vaeb_ctx* c);
-
-StepArgs make_args(vaeb_ctx* c, int par, int Mb, int mode, const float* xbase, bool train) {
-    StepArgs a{};
-    const vaeb_config& g = c->c;
-    a.D = g.D; a.H = g.H; a.Z = g.Z; a.L = g.L;
-    a.Mb = Mb; a.Mbp = r16(Mb); a.Me = g.L * a.Mbp;
-    a.dec = g.decoder; a.est = g.estimator == VAEB_EST_FVS ? VAEB_EST_LB : g.estimator; a.mode = mode;
-    a.sc = (g.objective == VAEB_OBJ_MEAN_MAP) ? 1.0f / (float)g.B_global : 1.0f;
-    const float* t = c->theta2[par];
-    const bool gs = gaussian(c);
-    // reference order: W3,W4,W5,W1,W2,(W6),b3,b4,b5,b1,b2,(b6)
-    a.W3 = t + c->off[0]; a.W4 = t + c->off[1]; a.W5 = t + c->off[2]; a.W1 = t + c->off[3];
-    a.W2 = t + c->off[4];
-    const int bo = gs ? 6 : 5;
-    a.W6 = gs ? t + c->off[5] : nullptr;
-    a.b3 = t + c->off[bo + 0]; a.b4 = t + c->off[bo + 1]; a.b5 = t + c->off[bo + 2];
-    a.b1 = t + c->off[bo + 3]; a.b2 = t + c->off[bo + 4];
-    a.b6 = gs ? t + c->off[bo + 5] : nullptr;
-    a.xbase = xbase;
-    if (train) {
-        // this rank's rows of global minibatch b start at row b * B_global + row_offset
-        a.xbase = xbase + (int64_t)g.row_offset * g.D;
-        a.order = c->ictl + kCtlOrder;
-        a.cursor = c->ictl;
-        a.cur_batch = c->ictl + 1;
-        a.batch_stride = (int64_t)g.B_global * g.D;
-        a.row_base_mul = g.B_global;
-        a.row_base_add = g.row_offset;
-        a.domain = 0;
-    } else {
-        a.order = nullptr; a.cursor = nullptr; a.cur_batch = c->ictl + 1;
-        a.batch_stride = 0; a.row_base_mul = 0; a.row_base_add = 0;
-        a.domain = 1;
-    }
-    a.eps_mode = (mode == MODE_RECON) ? 2 : (c->eps_mode == VAEB_EPS_HOST ? 1 : 0);
-    a.seed = c->seed;
-    a.step = c->step;
-    a.eps_in = c->eps_in;
-    a.eps_in_ld = c->eps_rows;
-    a.h = c->h; a.mu = c->mu; a.lv = c->lv; a.eps = c->eps; a.z = c->z; a.hd = c->hd; a.y = c->y;
-    a.dA2 = c->dA2; a.dA6 = c->dA6; a.dA1 = c->dA1; a.dZ = c->dZ; a.dMuLv = c->dMuLv; a.dA3 = c->dA3;
-    a.kl_part = c->kl_part; a.la_part = c->kl_part; a.lp_part = c->lp_part;
-    a.nctZ = cdiv(g.Z, 16);
-    a.nctD = cdiv(g.D, 16);
-    a.slab_ml = c->slab_ml; a.slab_dz = c->slab_dz; a.cnt_ml = c->cnt_ml; a.cnt_dz = c->cnt_dz;
-    a.acc_ml = c->acc_ml; a.acc_dz = c->acc_dz;
-    return a;
-}
-
-template <int WM, int WN, int KS, int NB, int GCH, class P>
-void launch_tile(hipStream_t s, const P& p) {
-    dim3 grid(cdiv(p.M, 16 * WM), cdiv(p.N, 16 * WN));
-    hipLaunchKernelGGL((tile_kernel<WM, WN, KS, NB, GCH, P>), grid, dim3(64 * WM * WN * KS), 0, s, p);
-}
-
-// Big-K phases: 8 waves split K; a wave's chunks go in flight together (GCH per trip).
-template <int NB, class P>
-void launch_bigk(hipStream_t s, const P& p) {
-    const int per_wave = cdiv(cdiv(p.K, 16), 8);
-    if (per_wave <= 4) launch_tile<1, 1, 8, NB, 4>(s, p);
-    else launch_tile<1, 1, 8, NB, 8>(s, p);
-}
-
-bool fused_latent(const vaeb_ctx* c) { return c->c.Z <= 32; }
-// Weight-gradient tile widths (columns; rows are kWT = 64).  Narrower tiles mean more
-// workgroups, each streaming fewer theta / accumulator / panel bytes through its CU: at
-// MNIST-20, 64 -> 32 wide took the dW2 launch 11.7 -> 9.5 us and the dW3 | dW45 launch
-// 10.9 -> 8.1 us; 16 wide takes the latter to 7.5 us but the dW2 launch (beside 224 dhd
-// tiles) back up to 11.1 us.
-constexpr int kWTJ_P5 = 32;    // dW2 (| dW6), beside the dhd tiles (64 wide: 40.1 vs 38.8 us per step)
-constexpr int kW3TS = 1;       // 16-column groups per tile of the last launch (dW3 | dW45 | dW1; 2: 40.1 vs 38.8)
-constexpr int kWTJ_P67 = 16;   // dW1, beside the dz / dh phase
-constexpr int kWTJ_W = 16;     // standalone launches: dW3 | dW45 (+ ELBO), non-fused dW1
-constexpr int kDzSplit = 8;    // P67 column splits per row block (fused.hpp dz_dh_body)
-
-// The deferred dW2's launch arguments (the previous step's dW2 (| dW6) group; vaeb_ctx::dw2_defer)
-struct W2Launch {
-    WGradArgs w;
-    bool vec;
-    const int* pend;
-    int width;     // tile columns (w2_plan)
-    bool paired;   // two tiles per workgroup, after the encoder rows
-};
-
-// The deferred dW2's tiling (latent.hpp enc_latent16_w2_kernel).  One 64 x width tile per
-// workgroup, each on a CU of its own beside the encoder's `enc_wgs` workgroups: the narrowest of
-// 32, 48 and 64 columns whose tile count fits the CUs left free (narrower tiles stream fewer
-// theta / Adagrad / panel bytes through one CU's load path; MNIST 784-500: 17 x 8 = 136 tiles
-// of 48 beside 112 encoder workgroups).  Where none fits (or VAEB_DW2_PAIRED=1): 32-wide tiles,
-// two per workgroup.  rows = H + 1 (the bias row), cols = D (Gaussian: [W2 | W6] = 2 D).
-// wide64: 64 columns are a candidate -- only with 16-byte accesses (the scalar epilogue's
-// per-element offsets, theta and Adagrad state of 64 columns do not fit 128 VGPRs).
-constexpr int kCUs = 256;
-struct W2Plan {
-    int width, paired, tiles_i, tiles_j;   // tile (row block i, column block j) = worker i * tiles_j + j
-};
-W2Plan w2_plan(int rows, int cols, int enc_wgs, bool force_paired, bool wide64) {
-    const int ti = cdiv(rows, kWT);
-    if (!force_paired)
-        for (int w : {32, 48, 64}) {
-            if (w == 64 && !wide64) break;
-            const int tj = cdiv(cols, w);
-            if (ti * tj <= kCUs - enc_wgs) return W2Plan{w, 0, ti, tj};
-        }
-    return W2Plan{kWTJ_P5, 1, ti, cdiv(cols, kWTJ_P5)};
-}
-
-// The folded latent hand-offs: counted fixed-point atomics (latent.hpp fx_*) or slabs +
-// ticket + reducer.  The returning adds to one accumulator serialise at the memory side, so
-// the atomic form wins only at a small fan-in (contributors per element): Frey 560-200-2
-// (13 column tiles) 38.5 -> 32.2 us per step; MNIST 784-500-20 (32 column tiles) 44.5 ->
-// 49.3 us.  Forward fan-in: the H column tiles; backward: H column tiles x L planes.
-// (A third form -- the same adds without return + the slab protocol's ticket, the last
-// arriver reading each sum with one exchange -- measured slower than both, MNIST 53.6 us,
-// Frey 35.0 us, and was removed in round 3.)  VAEB_ATOMIC_HO=0 forces the slabs.
-int ho_mode(const vaeb_ctx* c, int fan_in) {
-    if (c->atomic_ho == 0) return 0;
-    return fan_in <= kFxMaxFanIn ? 1 : 0;   // the count field holds <= 16 contributors (latent.hpp)
-}
-int ho_ml(const vaeb_ctx* c, int ct) { return ho_mode(c, cdiv(c->c.H, 16 * ct)); }
-bool dw2_deferrable(const vaeb_ctx* c);
-// backward: 1 atomic, else 2 (deferred to the last launch's reducers, VAEB_BWD_DEFER) or 0
-// (ticket).  (Round 5's form 3 -- two dA1 column tiles per 1024-thread dhd workgroup so MNIST's
-// fan-in fits the counted atomics -- measured 39.4 vs 34.4 us per step and was removed in round 6.)
-int ho_dz(const vaeb_ctx* c) {
-    const int m = ho_mode(c, cdiv(c->c.H, 16) * c->c.L);
-    return m == 0 && c->bwd_defer ? 2 : m;
+    int n = 0;   // the slots, in the same order
+    ArenaSlots& sl = c->sl;
+    sl.W3 = n++; sl.W4 = n++; sl.W5 = n++; sl.W1 = n++; sl.W2 = n++; sl.W6 = gs ? n++ : -1;
+    sl.b3 = n++; sl.b4 = n++; sl.b5 = n++; sl.b1 = n++; sl.b2 = n++; sl.b6 = gs ? n++ : -1;
 }
 
 // Measurement brackets: mark(id) records an event before launch slot `id`.  With
@@ -362,7 +261,7 @@ struct Prof {
     bool on;
     int reps = 1;
     int k = 0;
-    void mark(int id) {
+    void mark(KernelId id) {
         if (!on) return;
         hipEventRecord(c->pev[k], c->s);
         if (k < (int)c->prof_ids.size()) c->prof_ids[k] = id; else c->prof_ids.push_back(id);
@@ -370,612 +269,20 @@ struct Prof {
     }
 };
 
-ElboArgs base_elbo(vaeb_ctx* c, const StepArgs& a) {
-    ElboArgs e{};
-    e.lp_part = c->lp_part; e.n_lp = (int64_t)a.Me * a.nctD;
-    e.kl_part = c->kl_part;
-    e.n_kl = (int64_t)(c->c.estimator == VAEB_EST_LA ? a.Me : a.Mbp) * a.nctZ;
-    e.L = c->c.L; e.est = c->c.estimator;
-    e.data_mul = 1.0;
-    e.inv_bglob = 1.0 / (double)c->c.B_global;
-    return e;
-}
-
-template <int NB, bool V1, int AT>
-void launch_decout_zv(hipStream_t s, dim3 grid, const StepArgs& a, int ct) {
-    if (NB == 1 && ct == 2) {   // two column tiles per workgroup
-        switch ((a.Z + 3) / 4) {
-            case 1: hipLaunchKernelGGL((decout_z2_kernel<1, V1, AT>), grid, dim3(512), 0, s, a); break;
-            case 2: hipLaunchKernelGGL((decout_z2_kernel<2, V1, AT>), grid, dim3(512), 0, s, a); break;
-            case 3: case 4: hipLaunchKernelGGL((decout_z2_kernel<4, V1, AT>), grid, dim3(512), 0, s, a); break;
-            case 5: hipLaunchKernelGGL((decout_z2_kernel<5, V1, AT>), grid, dim3(512), 0, s, a); break;
-            default: hipLaunchKernelGGL((decout_z2_kernel<8, V1, AT>), grid, dim3(512), 0, s, a); break;
-        }
-        return;
-    }
-    switch ((a.Z + 3) / 4) {
-        case 1: hipLaunchKernelGGL((decout_z_kernel<NB, 1, V1, AT>), grid, dim3(512), 0, s, a); break;
-        case 2: hipLaunchKernelGGL((decout_z_kernel<NB, 2, V1, AT>), grid, dim3(512), 0, s, a); break;
-        case 3: case 4: hipLaunchKernelGGL((decout_z_kernel<NB, 4, V1, AT>), grid, dim3(512), 0, s, a); break;
-        case 5: hipLaunchKernelGGL((decout_z_kernel<NB, 5, V1, AT>), grid, dim3(512), 0, s, a); break;
-        default: hipLaunchKernelGGL((decout_z_kernel<NB, 8, V1, AT>), grid, dim3(512), 0, s, a); break;
-    }
-}
-template <int NB, int AT>
-void launch_decout_z(hipStream_t s, dim3 grid, const StepArgs& a, int ct = 1) {
-    auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    if ((a.H & 3) == 0 && al(a.W1) && al(a.b1)) launch_decout_zv<NB, true, AT>(s, grid, a, ct);
-    else launch_decout_zv<NB, false, AT>(s, grid, a, ct);
-}
-
-// dhd_dz_wgrad_kernel at compile-time NCT (latent col tiles), GCH, load width, AT
-template <int TS, int HO>
-void launch_dhd_dz(hipStream_t s, dim3 grid, const PDhdT<true>& p5, const PDhdT<false>& p5s, const WGradArgs& w,
-                   int ntile, int gx, bool vec, bool deep, DhdAux pend) {
-    if (p5.a.Z <= 16) {
-        if (deep) {
-            if (vec) hipLaunchKernelGGL((dhd_dz_wgrad_kernel<1, 8, true, TS, HO>), grid, dim3(512), 0, s, p5, w, ntile, gx, pend);
-            else hipLaunchKernelGGL((dhd_dz_wgrad_kernel<1, 8, false, TS, HO>), grid, dim3(512), 0, s, p5s, w, ntile, gx, pend);
-        } else {
-            if (vec) hipLaunchKernelGGL((dhd_dz_wgrad_kernel<1, 4, true, TS, HO>), grid, dim3(512), 0, s, p5, w, ntile, gx, pend);
-            else hipLaunchKernelGGL((dhd_dz_wgrad_kernel<1, 4, false, TS, HO>), grid, dim3(512), 0, s, p5s, w, ntile, gx, pend);
-        }
-    } else {
-        if (deep) {
-            if (vec) hipLaunchKernelGGL((dhd_dz_wgrad_kernel<2, 8, true, TS, HO>), grid, dim3(512), 0, s, p5, w, ntile, gx, pend);
-            else hipLaunchKernelGGL((dhd_dz_wgrad_kernel<2, 8, false, TS, HO>), grid, dim3(512), 0, s, p5s, w, ntile, gx, pend);
-        } else {
-            if (vec) hipLaunchKernelGGL((dhd_dz_wgrad_kernel<2, 4, true, TS, HO>), grid, dim3(512), 0, s, p5, w, ntile, gx, pend);
-            else hipLaunchKernelGGL((dhd_dz_wgrad_kernel<2, 4, false, TS, HO>), grid, dim3(512), 0, s, p5s, w, ntile, gx, pend);
-        }
-    }
-}
-
-// enc_latent_kernel / enc_latent_fv_kernel at compile-time NCT (latent col tiles), GCH
-// (main-loop chunk group), AT (atomic hand-off)
-template <int HO, int CT>
-void launch_enc_latent_ct(hipStream_t s, dim3 g1, const StepArgs& a, const FvFold& fvf, bool deep) {
-    if (fvf.rows > 0) {
-        if (a.Z <= 16) {
-            if (deep) hipLaunchKernelGGL((enc_latent_fv_kernel<1, 8, HO, CT>), g1, dim3(512), 0, s, a, fvf);
-            else hipLaunchKernelGGL((enc_latent_fv_kernel<1, 4, HO, CT>), g1, dim3(512), 0, s, a, fvf);
-        } else {
-            if (deep) hipLaunchKernelGGL((enc_latent_fv_kernel<2, 8, HO, CT>), g1, dim3(512), 0, s, a, fvf);
-            else hipLaunchKernelGGL((enc_latent_fv_kernel<2, 4, HO, CT>), g1, dim3(512), 0, s, a, fvf);
-        }
-    } else if (a.Z <= 16) {
-        if (deep) hipLaunchKernelGGL((enc_latent_kernel<1, 8, HO, CT>), g1, dim3(512), 0, s, a);
-        else hipLaunchKernelGGL((enc_latent_kernel<1, 4, HO, CT>), g1, dim3(512), 0, s, a);
-    } else {
-        if (deep) hipLaunchKernelGGL((enc_latent_kernel<2, 8, HO, CT>), g1, dim3(512), 0, s, a);
-        else hipLaunchKernelGGL((enc_latent_kernel<2, 4, HO, CT>), g1, dim3(512), 0, s, a);
-    }
-}
-// The 16-wave encoder with the deferred dW2 workers (w2: the previous step's dW2 group) in
-// ceil(workgroups / (Mbp / 16)) extra grid rows: ahead of the encoder rows with one tile per
-// workgroup, behind them in the paired form (and in the timeline build, whose stamps index the
-// encoder's workgroups from 0).
-template <int HO, int CT, int TS, int NW>
-void launch_enc16_w2_ts(hipStream_t s, dim3 g1, const StepArgs& a, const W2Launch& w2) {
-    const int rows_enc = (int)g1.y, rows_w2 = cdiv(cdiv(w2.w.total_wgs, NW), (int)g1.x);
-#ifdef VAEB_TIMELINE
-    const bool first = false;
-#else
-    const bool first = NW == 1;
-#endif
-    const int y_enc = first ? rows_w2 : 0, y_w2 = first ? 0 : rows_enc;
-    const dim3 g(g1.x, rows_enc + rows_w2);
-    if constexpr (TS == 4) {   // 64 columns: planned only with 16-byte accesses (w2_plan)
-        if (a.Z <= 16) hipLaunchKernelGGL((enc_latent16_w2_kernel<1, 4, HO, CT, true, TS, NW>), g, dim3(1024), 0, s, a, w2.w, w2.pend, y_enc, y_w2, rows_w2);
-        else hipLaunchKernelGGL((enc_latent16_w2_kernel<2, 4, HO, CT, true, TS, NW>), g, dim3(1024), 0, s, a, w2.w, w2.pend, y_enc, y_w2, rows_w2);
-    } else if (a.Z <= 16) {
-        if (w2.vec) hipLaunchKernelGGL((enc_latent16_w2_kernel<1, 4, HO, CT, true, TS, NW>), g, dim3(1024), 0, s, a, w2.w, w2.pend, y_enc, y_w2, rows_w2);
-        else hipLaunchKernelGGL((enc_latent16_w2_kernel<1, 4, HO, CT, false, TS, NW>), g, dim3(1024), 0, s, a, w2.w, w2.pend, y_enc, y_w2, rows_w2);
-    } else {
-        if (w2.vec) hipLaunchKernelGGL((enc_latent16_w2_kernel<2, 4, HO, CT, true, TS, NW>), g, dim3(1024), 0, s, a, w2.w, w2.pend, y_enc, y_w2, rows_w2);
-        else hipLaunchKernelGGL((enc_latent16_w2_kernel<2, 4, HO, CT, false, TS, NW>), g, dim3(1024), 0, s, a, w2.w, w2.pend, y_enc, y_w2, rows_w2);
-    }
-}
-template <int HO, int CT>
-void launch_enc16_w2(hipStream_t s, dim3 g1, const StepArgs& a, const W2Launch& w2) {
-    if (w2.paired) launch_enc16_w2_ts<HO, CT, kWTJ_P5 / 16, 2>(s, g1, a, w2);
-    else if (w2.width == 32) launch_enc16_w2_ts<HO, CT, 2, 1>(s, g1, a, w2);
-    else if (w2.width == 48) launch_enc16_w2_ts<HO, CT, 3, 1>(s, g1, a, w2);
-    else launch_enc16_w2_ts<HO, CT, 4, 1>(s, g1, a, w2);
-}
-
-// The slab-only encoder (HO 3: partials summed by the decoder launch, CT = 2, no FV) and the
-// atomic hand-off encoder (HO 1, one column tile, no FV) run on 1024-thread workgroups, 16
-// waves splitting K (twice the loads in flight per CU): MNIST 38.82 -> 37.87 us/step, Frey
-// 29.19 -> 29.01 in round 3's alternating runs (the 512-thread forms' switch, VAEB_ENC16, was
-// removed in round 6).  The ticketed reducer (HO 0) and the FV-stream encoder keep 512 threads.
-template <int HO>
-void launch_enc_latent(hipStream_t s, dim3 g1, const StepArgs& a, const FvFold& fvf, bool deep, int ct,
-                       const W2Launch* w2 = nullptr) {
-    if constexpr (HO == 3) {
-        if (w2) { launch_enc16_w2<HO, 2>(s, g1, a, *w2); return; }
-        if (a.Z <= 16) hipLaunchKernelGGL((enc_latent16_kernel<1, 4, HO, 2>), g1, dim3(1024), 0, s, a);
-        else hipLaunchKernelGGL((enc_latent16_kernel<2, 4, HO, 2>), g1, dim3(1024), 0, s, a);
-        return;
-    }
-    if (HO == 1 && fvf.rows == 0 && ct == 1) {   // the atomic hand-off on 16 waves
-        if constexpr (HO == 1) if (w2) { launch_enc16_w2<1, 1>(s, g1, a, *w2); return; }
-        if (a.Z <= 16) hipLaunchKernelGGL((enc_latent16_kernel<1, 4, 1, 1>), g1, dim3(1024), 0, s, a);
-        else hipLaunchKernelGGL((enc_latent16_kernel<2, 4, 1, 1>), g1, dim3(1024), 0, s, a);
-        return;
-    }
-    if (ct == 2) launch_enc_latent_ct<HO, 2>(s, g1, a, fvf, deep);
-    else launch_enc_latent_ct<HO, 1>(s, g1, a, fvf, deep);
-}
-
-// Training minibatches with Z <= 32 fold the latent block into the wide phases
-// (latent.hpp); validation / reconstruction chunks keep the per-row-block kernels.
-bool folded_latent(const vaeb_ctx* c, const StepArgs& a) {
-    return fused_latent(c) && a.domain == 0 && a.Mbp <= r16(c->c.B);   // training rows (domain 0)
-}
-
-// Forward phases P1..P4 for any mode.
-// The encoder form the folded forward takes for `a` (enqueue_forward): ho (3 slabs summed by
-// the decoder, 1 counted atomics, 0 ticket), ct column tiles per workgroup; true when that
-// form runs on 16-wave workgroups (enc_latent16_kernel), the one that can carry the deferred dW2.
-bool enc_form(const vaeb_ctx* c, const StepArgs& a, const FvFold& fvf, int* ho_out, int* ct_out, bool* red_out) {
-    const bool red = (c->enc_red < 0 ? ho_ml(c, 1) == 0 : c->enc_red == 1) && fvf.rows == 0 && cdiv(a.H, 32) <= 32;
-    const int ct = (red || fvf.rows > 0) ? 2 : 1;
-    // (round 4's HO 4 -- the [mu | lv] partials as exact fixed-point sums read by the decoder,
-    // VAEB_ENC_FX -- measured 34.8-35.1 vs 34.4-34.5 us per step and was removed in round 6)
-    const int ho = red ? 3 : ho_ml(c, ct);
-    if (ho_out) *ho_out = ho;
-    if (ct_out) *ct_out = ct;
-    if (red_out) *red_out = red;
-    return ho == 3 || (ho == 1 && fvf.rows == 0 && ct == 1);
-}
-
-int enqueue_forward(vaeb_ctx* c, const StepArgs& a0, Prof& pr, const FvFold& fvf = FvFold{},
-                    const W2Launch* w2 = nullptr) {
-    hipStream_t s = c->s;
-    StepArgs a = a0;
-    a.dbg = next_dbg(c);
-    if (folded_latent(c, a)) {
-        // auto: two column tiles per workgroup when the literal-FV stream shares the launch
-        // (FV 27.75 -> 27.4 us: fewer encoder tiles beside the stream blocks), else one
-        // (MNIST 44.6 either way, Frey 32.2 vs 34.0 us)
-        // VAEB_ENC_RED=1: no hand-off in the encoder launch at all -- its CT = 2 tiles store
-        // partial [mu | lv] slabs and end; every decoder workgroup sums its row block's
-        // ceil(H / 32) slabs (decout_z_kernel<.., ZM = 2>)
-        // auto: where the slab + ticket form would be chosen (fan-in > 16; MNIST 784-500-20
-        // 43.8 -> 42.5 us); at a small fan-in the counted atomics stay (Frey 30.8 vs 32.7 us)
-        int ho, ct;
-        bool red;
-        enc_form(c, a, fvf, &ho, &ct, &red);
-        const dim3 g1(a.Mbp / 16, cdiv(a.H, 16 * ct) + fvf.rows);
-        const bool deep = cdiv(cdiv(a.D, 16), 8) > 4;
-        const int at = red ? 2 : (ho == 1 ? 1 : 0);
-        pr.mark(w2 ? 42 : 16);
-        REP(pr) {
-            if (ho == 3) launch_enc_latent<3>(s, g1, a, fvf, deep, ct, w2);
-            else if (ho == 1) launch_enc_latent<1>(s, g1, a, fvf, deep, ct, w2);
-            else launch_enc_latent<0>(s, g1, a, fvf, deep, ct);
-        }
-        CHECK_LAUNCH();
-        if (int rc = order_hook(c)) return rc;
-        a.dbg = next_dbg(c);
-        // Bernoulli: two 16-column tiles per workgroup (decout_z2_kernel; one tile: 42.0 vs
-        // 39.4 us per step in round 3, its switch VAEB_DECOUT_CT removed in round 6)
-        const int dct = gaussian(c) ? 1 : 2;
-        const dim3 g4(a.Me / 16, cdiv(a.D, 16 * dct));
-        pr.mark(17);
-        REP(pr) {
-            if (gaussian(c)) {
-                if (at == 2) launch_decout_z<2, 2>(s, g4, a);
-                else if (at == 1) launch_decout_z<2, 1>(s, g4, a);
-                else launch_decout_z<2, 0>(s, g4, a);
-            } else {
-                if (at == 2) launch_decout_z<1, 2>(s, g4, a, dct);
-                else if (at == 1) launch_decout_z<1, 1>(s, g4, a, dct);
-                else launch_decout_z<1, 0>(s, g4, a, dct);
-            }
-        }
-        CHECK_LAUNCH();
-        return 0;
-    }
-    pr.mark(0);
-    REP(pr) launch_bigk<1>(s, PEnc{a, nullptr, a.Mbp, a.H, a.D});
-    CHECK_LAUNCH();
-    a.dbg = next_dbg(c);
-    if (fused_latent(c)) {
-        pr.mark(12);
-        REP(pr) {
-            if (a.Z <= 16) hipLaunchKernelGGL(heads_dechid_kernel<1>, dim3(a.Mbp / 16), dim3(512), 0, s, a);
-            else hipLaunchKernelGGL(heads_dechid_kernel<2>, dim3(a.Mbp / 16), dim3(512), 0, s, a);
-        }
-        CHECK_LAUNCH();
-    } else {
-        pr.mark(1);
-        REP(pr) launch_tile<1, 1, 4, 2, 8>(s, PHeads{a, a.Mbp, a.Z, a.H});
-        CHECK_LAUNCH();
-        pr.mark(2);
-        REP(pr) launch_tile<1, 4, 1, 1, 8>(s, PDecHid{a, a.Me, a.H, a.Z});
-        CHECK_LAUNCH();
-    }
-    a.dbg = next_dbg(c);
-    pr.mark(3);
-    REP(pr) {
-        if (gaussian(c)) launch_bigk<2>(s, PDecOut{a, nullptr, a.Me, a.D, a.H});
-        else launch_bigk<1>(s, PDecOut{a, nullptr, a.Me, a.D, a.H});
-    }
+// The order upload update_many held back for its eager first step (vaeb_ctx::order_pending):
+// launched right after that step's first kernel, or after the step where no launch site
+// takes it.  The eager step addresses its rows from its launch arguments and reads neither the
+// order nor the cursor, so the upload may run between its launches.
+int order_hook(vaeb_ctx* c) {
+    if (!c->order_pending) return 0;
+    c->order_pending = false;
+    hipLaunchKernelGGL(set_order_kernel, dim3(1), dim3(256), 0, c->s, c->ictl, c->order_pend);
     CHECK_LAUNCH();
     return 0;
 }
 
-OptArgs make_opt(vaeb_ctx* c, int par, bool update, bool store) {
-    OptArgs o{};
-    o.theta_in = c->theta2[par];
-    o.theta_out = c->theta2[par ^ 1];
-    o.acc = c->acc; o.grad = c->grad;
-    o.lr = c->c.lr; o.eps = c->c.adagrad_eps;
-    const bool mean = c->c.objective == VAEB_OBJ_MEAN_MAP;
-    o.prior = mean ? 0.f : 1.f;
-    o.decay = mean ? c->c.lr * c->c.adagrad_eps : 0.f;
-    o.update = update ? 1 : 0;
-    o.store_grad = store ? 1 : 0;
-    return o;
-}
-
-// 16-byte dhd operand loads (PDhdT<true>): D % 4 == 0 and 16-byte aligned dA2 / W2 (the
-// Gaussian halves dA6 / W6 then are too: they sit a multiple of 4 elements further).
-bool dhd_vec(const StepArgs& a) {
-    auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    return (a.D & 3) == 0 && al(a.dA2) && al(a.W2);
-}
-
-
-void set_head(WGradArgs& w, int n, int total, bool elbo, const float* xb, const int* cb, int64_t bs) {
-    w.ngroups = n; w.total_wgs = total; w.with_elbo = elbo; w.xbase = xb; w.cur_batch = cb; w.batch_stride = bs;
-}
-void set_head(WGradArgs3& w, int n, int total, bool elbo, const float* xb, const int* cb, int64_t bs) {
-    W3Head& h = w.hd;
-    h.ngroups = n; h.total_wgs = total; h.with_elbo = elbo; h.xbase = xb; h.cur_batch = cb; h.batch_stride = bs;
-    h.gb1 = n > 1 ? w.g[1].wg_begin : total; h.gb2 = n > 2 ? w.g[2].wg_begin : total;
-    h.nred = 0; h.red_cnt = nullptr;
-}
-int total_wgs(const WGradArgs& w) { return w.total_wgs; }
-int total_wgs(const WGradArgs3& w) { return w.hd.total_wgs; }
-
-// Weight-gradient arguments over `n` groups whose tiles start at block `base` of the
-// launch (+ the ELBO workgroup when e != nullptr).  *vec: 16-byte panel loads are legal.
-template <class WA>
-int prep_wgrad(vaeb_ctx* c, const WGroup* groups, int n, const OptArgs& opt, const ElboArgs* e, const StepArgs& a,
-               int base, WA& w, bool& vec, int tw, int* vmask = nullptr) {
-    w = WA{};
-    int begin = base;
-    constexpr int kMaxG = (int)(sizeof(w.g) / sizeof(w.g[0]));
-    if (n < 1 || n > kMaxG) return fail(VAEB_ERR_ARG, "internal: 1 to %d weight-gradient groups per launch", kMaxG);
-    for (int gi = 0; gi < n; ++gi) {
-        w.g[gi] = groups[gi];
-        WGroup& G = w.g[gi];
-        G.tiles_j = cdiv(G.N0 + G.N1, tw);
-        G.wg_begin = begin;
-        G.wg_end = begin + cdiv(G.rowsW + 1, kWT) * G.tiles_j;
-        begin = G.wg_end;
-    }
-    set_head(w, n, begin, e != nullptr, a.xbase, c->ictl + 1, a.batch_stride);
-    w.opt = opt;
-    if (e) w.elbo = *e;
-    w.P = c->P;
-    w.dbg = a.dbg;
-    // 16-byte panel loads need every panel row aligned with widths % 4 == 0 (the
-    // activation buffers are hipMalloc'd; X rows are D floats apart)
-    vec = true;
-    if (vmask) *vmask = 0;
-    auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    for (int gi = 0; gi < n; ++gi) {
-        const WGroup& G = w.g[gi];
-        // (and 16-byte theta / Adagrad-state accesses in the epilogue: arena offsets % 4 == 0)
-        const bool gv = (G.ld_at % 4 == 0) && (G.rowsW % 4 == 0) && (G.at_is_x ? al(a.xbase) : al(G.at)) &&
-                        (G.ld0 % 4 == 0) && (G.N0 % 4 == 0) && al(G.b0) && G.offW0 % 4 == 0 && G.offb0 % 4 == 0 &&
-                        (G.N1 == 0 || ((G.ld1 % 4 == 0) && (G.N1 % 4 == 0) && al(G.b1) && G.offW1 % 4 == 0 &&
-                                       G.offb1 % 4 == 0)) &&
-                        al(c->theta2[0]) && al(c->theta2[1]) && al(c->acc) && al(c->grad);
-        vec = vec && gv;
-        if (vmask && gv) *vmask |= 1 << gi;
-    }
-    return 0;
-}
-
-// A standalone weight-gradient launch (256-thread blocks).  da3: group 0 (dW3) forms its
-// dA3 panel from [dMu | dLv] in the workgroup (the folded latent backward).
-int launch_wgrad(vaeb_ctx* c, hipStream_t s, const WGroup* groups, int n, const OptArgs& opt, const ElboArgs* e,
-                 const StepArgs& a, const Da3Src* da3 = nullptr) {
-    bool vec;
-    if (da3) {
-        if (n != 3) return fail(VAEB_ERR_ARG, "internal: the dA3-forming launch takes three groups");
-        WGradArgs3 w;
-        // 16-column tiles (32-wide: MNIST 46.3 vs 44.7 us, Frey 41.5 vs 38.4 in round 2;
-        // -DVAEB_W3_TS=2 builds them for A/B)
-        int vm = 0;   // 16-byte panel loads per group (Frey: dW3 yes, dW4 | dW5 and dW1 not)
-        if (int rc = prep_wgrad(c, groups, n, opt, e, a, 0, w, vec, 16 * kW3TS, &vm)) return rc;
-        w.da3 = *da3;
-        const int nred = da3->red.nred;
-        w.hd.nred = nred;
-        w.hd.red_cnt = da3->red.cnt;
-        const dim3 grid(w.hd.total_wgs + (e ? 1 : 0) + nred);
-        auto go = [&](auto DF) {
-            constexpr bool df = decltype(DF)::value;
-            switch (vm) {
-                case 7: hipLaunchKernelGGL((wgrad3_kernel<7, kW3TS, df>), grid, dim3(256), 0, s, w); break;
-                case 1: hipLaunchKernelGGL((wgrad3_kernel<1, kW3TS, df>), grid, dim3(256), 0, s, w); break;
-                case 3: hipLaunchKernelGGL((wgrad3_kernel<3, kW3TS, df>), grid, dim3(256), 0, s, w); break;
-                case 5: hipLaunchKernelGGL((wgrad3_kernel<5, kW3TS, df>), grid, dim3(256), 0, s, w); break;
-                default: hipLaunchKernelGGL((wgrad3_kernel<0, kW3TS, df>), grid, dim3(256), 0, s, w); break;
-            }
-        };
-        // DEFER: reducers in this launch, or [dMu | dLv] handed in by the dhd launch
-        if (nred > 0) go(std::true_type{});
-        else go(std::false_type{});
-    } else {
-        WGradArgs w;
-        if (int rc = prep_wgrad(c, groups, n, opt, e, a, 0, w, vec, kWTJ_W)) return rc;
-        const dim3 grid(w.total_wgs + (e ? 1 : 0));
-        if (vec) hipLaunchKernelGGL((wgrad_kernel<true, kWTJ_W / 16>), grid, dim3(256), 0, s, w);
-        else hipLaunchKernelGGL((wgrad_kernel<false, kWTJ_W / 16>), grid, dim3(256), 0, s, w);
-    }
-    CHECK_LAUNCH();
-    return 0;
-}
-
-WGroup make_group(vaeb_ctx* c, const float* at, int ld_at, int klim, int at_is_x, int rowsW, const float* b0, int ld0,
-                  int N0, const float* b1, int ld1, int N1, int K, int pW0, int pb0, int pW1, int pb1) {
-    WGroup G{};
-    G.at = at; G.ld_at = ld_at; G.klim_at = klim; G.at_is_x = at_is_x; G.rowsW = rowsW;
-    G.b0 = b0; G.ld0 = ld0; G.N0 = N0; G.b1 = b1; G.ld1 = ld1; G.N1 = N1; G.K = K;
-    G.offW0 = c->off[pW0]; G.offb0 = c->off[pb0];
-    G.offW1 = pW1 >= 0 ? c->off[pW1] : 0; G.offb1 = pb1 >= 0 ? c->off[pb1] : 0;
-    return G;
-}
-
-// The dW2 (| dW6) weight-gradient group -- [hd | 1]^T [dA2 (| dA6)] -- as launch arguments
-// whose tiles start at block `base`, with the optimizer `opt`.
-int w2_args(vaeb_ctx* c, const StepArgs& a, const OptArgs& opt, int base, WGradArgs& w, bool& vec, int tw = kWTJ_P5) {
-    const bool gs = gaussian(c);
-    const int bo = gs ? 6 : 5;
-    WGroup g4 = make_group(c, c->hd, a.H, a.Me, 0, a.H, c->dA2, a.D, a.D, gs ? c->dA6 : nullptr, a.D, gs ? a.D : 0,
-                           a.Me, 4, bo + 4, gs ? 5 : -1, gs ? bo + 5 : -1);
-    return prep_wgrad(c, &g4, 1, opt, nullptr, a, base, w, vec, tw);
-}
-// The deferred dW2's tiling for the training step on `a` (its encoder grid: enqueue_forward).
-W2Plan w2_plan_for(const vaeb_ctx* c, const StepArgs& a) {
-    int ct = 1;
-    enc_form(c, a, FvFold{}, nullptr, &ct, nullptr);
-    // prep_wgrad's conditions on the dW2 group's widths and arena offsets for 16-byte accesses
-    // (its pointers are device allocations, always aligned)
-    const bool gs = gaussian(c);
-    const int bo = gs ? 6 : 5;
-    const bool vec = a.H % 4 == 0 && a.D % 4 == 0 && c->off[4] % 4 == 0 && c->off[bo + 4] % 4 == 0 &&
-                     (!gs || (c->off[5] % 4 == 0 && c->off[bo + 5] % 4 == 0));
-    return w2_plan(a.H + 1, (gs ? 2 : 1) * a.D, (a.Mbp / 16) * cdiv(a.H, 16 * ct), c->dw2_paired, vec);
-}
-
-// Whether the step on `a` defers its dW2 into the next step's encoder launch (vaeb_ctx::dw2_defer).
-// Only where the dhd launch hands its latent backward to the last launch (ho_dz 2): there the
-// dW2 tiles bound the dhd launch.  With the counted atomic backward (small fan-in: Frey) the dhd
-// launch is bound by that hand-off and hides dW2, while the encoder would pay for it: Frey
-// 29.78 / 29.87 µs in-step vs 31.54 / 31.55 deferred.
-bool dw2_deferrable(const vaeb_ctx* c) {
-    const int est = c->c.estimator;
-    StepArgs a{};
-    a.H = c->c.H;   // (all enc_form reads of the training step's arguments)
-    return c->dw2_defer && c->c.dtype == VAEB_DTYPE_F32 && c->comm == nullptr && est != VAEB_EST_FV && est != VAEB_EST_FVS &&
-           fused_latent(c) && c->fold_bwd && enc_form(c, a, FvFold{}, nullptr, nullptr, nullptr);
-}
-bool dw2_deferred(const vaeb_ctx* c, const StepArgs& a) {
-    const int hd = ho_dz(c);
-    return dw2_deferrable(c) && hd == 2 && folded_latent(c, a);
-}
-
-// Run the pending step's dW2 (| dW6) + Adagrad now (their own launch; the device flag makes it
-// a no-op when a later step's encoder already ran them): every host read or write of the
-// parameters, the Adagrad state or the gradient, every evaluation, comes after it.
-int w2_flush(vaeb_ctx* c) {
-    if (!c || !c->w2_dirty) return 0;
-    c->w2_dirty = false;
-    const int par = c->par;   // the arena the next step reads: the pending dW2 writes W2' there
-    StepArgs a = make_args(c, par, c->c.B, MODE_TRAIN, c->data, true);
-    WGradArgs w;
-    bool vec;
-    const int tw = w2_plan_for(c, a).width;   // the width of the deferred launch this one replaces
-    if (int rc = w2_args(c, a, make_opt(c, par ^ 1, true, c->c.keep_grads != 0), 0, w, vec, tw)) return rc;
-    w.dbg = nullptr;
-    if (tw == 64 && !vec) return fail(VAEB_ERR_ARG, "internal: 64-wide dW2 tiles need 16-byte accesses");
-    auto go = [&](auto TS) {
-        constexpr int ts = decltype(TS)::value;
-        if (vec) hipLaunchKernelGGL((w2_flush_kernel<true, ts>), dim3(w.total_wgs), dim3(512), 0, c->s, w, c->w2pend);
-        else if constexpr (ts < 4) hipLaunchKernelGGL((w2_flush_kernel<false, ts>), dim3(w.total_wgs), dim3(512), 0, c->s, w, c->w2pend);
-    };
-    if (tw == 32) go(std::integral_constant<int, 2>{});
-    else if (tw == 48) go(std::integral_constant<int, 3>{});
-    else go(std::integral_constant<int, 4>{});
-    CHECK_LAUNCH();
-    HIP_TRY(hipMemsetAsync(c->w2pend, 0, sizeof(int), c->s));
-    return 0;
-}
-
-// ------------------------------------------------------------------ DP gradient buckets
-// Arena order W3 W4 W5 W1 W2 [W6] b3 b4 b5 b1 b2 [b6] | SGVB.  Bucket A = W2 [| W6] is final
-// once the dW2 (| dW6) launch has run, early in the backward; bucket B = the rest plus the
-// SGVB slot, final after the last weight-gradient launch.  Unprofiled steps fork bucket A's
-// all-reduce and Adagrad onto s2, where they overlap the remaining backward launches; s
-// then waits for bucket A's all-reduce (RCCL calls on one communicator stay serialised, in
-// the same order on every rank), reduces bucket B itself, runs its Adagrad and waits for
-// bucket A's Adagrad.  Only the fork sits on s2's queue: the critical path on s keeps its
-// own queue, and both waits are normally satisfied by the time s reaches them.  Profiled
-// steps run one all-reduce and one optimizer launch on s (per-kernel timing).
-// The fork costs ~18 us per step on the fp32 engine's 58-us MNIST step at world 1 (hipGraph
-// with a second branch; 78 vs 60 us) -- more than a 1.6-MB bucket's all-reduce can hide --
-// so it is the bf16 engine's default only, where bucket A is 34 MB (config 5) and its
-// Adagrad alone (37 us) pays for the fork already at world 1 (933 vs ~940 us).
-// Sharded form (vaeb_ctx::dp_shard, world > 1): instead of all-reducing the
-// whole bucket and running the replicated Adagrad over all of it on every rank, each rank
-// reduce-scatters the bucket, updates ITS 1/W shard (prior + Adagrad; bf16: + shadow), and the
-// shards of theta' are all-gathered: the same xGMI bytes as the all-reduce (a ring all-reduce
-// is a reduce-scatter + all-gather), the optimizer stream per rank W times shorter, and every
-// replica bitwise identical (theta' comes from one owner).  Shards are 64-element aligned; the
-// remainder of each run (< 64 W elements, and the SGVB slot) is all-reduced and updated on
-// every rank.  The arena is always partitioned into the same three runs -- B0 = [0, W2),
-// A = [W2, b3) (W2 | W6), B1 = [b3, P) -- so an element's owner (and its Adagrad state, kept
-// on the owner only) is the same whichever bucket form a step takes.
-struct DpBucket {
-    int nrun;
-    int64_t lo[3], n[3];
-    bool slot;   // + grad[P] (the SGVB), right after the run that ends at P (the last one)
-};
-DpBucket dp_bucket_a_runs(const vaeb_ctx* c) {
-    const int bo = gaussian(c) ? 6 : 5;
-    return DpBucket{1, {c->off[4], 0, 0}, {c->off[bo] - c->off[4], 0, 0}, false};
-}
-DpBucket dp_bucket_b_runs(const vaeb_ctx* c) {
-    const int bo = gaussian(c) ? 6 : 5;
-    return DpBucket{2, {0, c->off[bo], 0}, {c->off[4], c->P - c->off[bo], 0}, true};
-}
-DpBucket dp_bucket_all_runs(const vaeb_ctx* c) {
-    const int bo = gaussian(c) ? 6 : 5;
-    return DpBucket{3, {0, c->off[4], c->off[bo]}, {c->off[4], c->off[bo] - c->off[4], c->P - c->off[bo]}, true};
-}
-// elements per rank of a run of n (0: the run is all-reduced and updated everywhere)
-int64_t dp_shard_len(const vaeb_ctx* c, int64_t n) { return c->dp_shard ? (n / c->world) & ~(int64_t)63 : 0; }
-// what this rank's optimizer launch updates: each run's own shard and its replicated remainder
-DpRange dp_opt_range(const vaeb_ctx* c, const DpBucket& bk) {
-    DpRange r{};
-    int k = 0;
-    for (int j = 0; j < bk.nrun; ++j) {
-        const int64_t S = dp_shard_len(c, bk.n[j]), tail = bk.n[j] - c->world * S;
-        if (S) { r.lo[k] = bk.lo[j] + c->rank * S; r.n[k++] = S; }
-        if (tail) { r.lo[k] = bk.lo[j] + c->world * S; r.n[k++] = tail; }
-    }
-    r.book = bk.slot ? 1 : 0;
-    return r;
-}
-// the elements of the bucket other ranks updated (their shards): the bf16 shadow fix
-DpRange dp_foreign_range(const vaeb_ctx* c, const DpBucket& bk) {
-    DpRange r{};
-    int k = 0;
-    for (int j = 0; j < bk.nrun; ++j) {
-        const int64_t S = dp_shard_len(c, bk.n[j]);
-        if (!S) continue;
-        if (c->rank > 0) { r.lo[k] = bk.lo[j]; r.n[k++] = c->rank * S; }
-        if (c->rank < c->world - 1) { r.lo[k] = bk.lo[j] + (c->rank + 1) * S; r.n[k++] = (c->world - c->rank - 1) * S; }
-    }
-    return r;
-}
-
-// The fp32 engine's DP optimizer launch over range r (prior + Adagrad; r.book: also the SGVB
-// bookkeeping): the step's dp_opt, and what vaeb_dp_rank_update runs for one emulated rank.
-int dp_opt_launch(vaeb_ctx* c, hipStream_t st, const OptArgs& o, const DpRange& r, const ElboArgs& e) {
-    int64_t n = 0;
-    for (int k = 0; k < kDpRuns; ++k) n += r.n[k];
-    // (sharded: a 1/W share of the arena; the grid scales down with it)
-    const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(r.book ? 512 : 256, cdiv(n, 256 * 8)));
-    hipLaunchKernelGGL(adagrad_kernel, dim3(nb), dim3(256), 0, st, o, c->P, r, e);
-    CHECK_LAUNCH();
-    return 0;
-}
-
-int nccl_ok(ncclResult_t r, const char* what) {
-    return r == ncclSuccess ? 0 : fail(VAEB_ERR_COMM, "%s: %s", what, ncclGetErrorString(r));
-}
-int nccl_sum(vaeb_ctx* c, float* p, int64_t n, hipStream_t st) {
-    return nccl_ok(ncclAllReduce(p, p, (size_t)n, ncclFloat, ncclSum, c->comm, st), "ncclAllReduce");
-}
-
-// One bucket on stream st: the reduction (reduce-scatter of each run's shards + all-reduce of
-// the remainders and the slot, one RCCL group), this rank's optimizer launch, then (sharded)
-// the all-gather of theta' shards and fix(st, foreign range) for the bf16 shadow.  comm_done
-// (if any) is recorded after the bucket's last collective: another stream's collectives wait
-// for it (RCCL calls on one communicator stay serialised, in the same order on every rank).
-template <class Opt, class Fix>
-int dp_reduce_update(vaeb_ctx* c, hipStream_t st, const DpBucket& bk, float* theta_out, Opt opt, Fix fix,
-                     hipEvent_t comm_done, Prof* pr = nullptr, int opt_mark = -1) {
-    const int W = c->world, rk = c->rank;
-    bool sharded = false;
-    if (pr) pr->mark(8);
-    for (int rep = 0; rep < (pr ? pr->reps : 1); ++rep) {
-        if (int rc = nccl_ok(ncclGroupStart(), "ncclGroupStart")) return rc;
-        int rc = 0;
-        for (int j = 0; j < bk.nrun && !rc; ++j) {
-            const int64_t S = dp_shard_len(c, bk.n[j]);
-            const int64_t tail = bk.n[j] - W * S + ((bk.slot && j == bk.nrun - 1) ? 1 : 0);
-            float* g = c->grad + bk.lo[j];
-            if (S) {
-                sharded = true;
-                rc = nccl_ok(ncclReduceScatter(g, g + rk * S, (size_t)S, ncclFloat, ncclSum, c->comm, st),
-                             "ncclReduceScatter");
-            }
-            if (!rc && tail) rc = nccl_sum(c, g + W * S, tail, st);
-        }
-        const int re = nccl_ok(ncclGroupEnd(), "ncclGroupEnd");
-        if (rc) return rc;
-        if (re) return re;
-    }
-    if (comm_done && !sharded) HIP_TRY(hipEventRecord(comm_done, st));
-    if (pr) pr->mark(opt_mark);
-    for (int rep = 0; rep < (pr ? pr->reps : 1); ++rep)
-        if (int rc = opt(st, dp_opt_range(c, bk))) return rc;
-    if (!sharded) return 0;
-    if (int rc = nccl_ok(ncclGroupStart(), "ncclGroupStart")) return rc;
-    int rc = 0;
-    for (int j = 0; j < bk.nrun && !rc; ++j) {
-        const int64_t S = dp_shard_len(c, bk.n[j]);
-        float* t = theta_out + bk.lo[j];
-        if (S) rc = nccl_ok(ncclAllGather(t + rk * S, t, (size_t)S, ncclFloat, c->comm, st), "ncclAllGather");
-    }
-    const int re = nccl_ok(ncclGroupEnd(), "ncclGroupEnd");
-    if (rc) return rc;
-    if (re) return re;
-    if (comm_done) HIP_TRY(hipEventRecord(comm_done, st));
-    return fix(st, dp_foreign_range(c, bk));
-}
-
-// Sharded Adagrad keeps each element's accumulator on its owner only: gather the shards before
-// the host reads the state (vaeb_get_adagrad_state, vaeb_checkpoint_save; every rank calls it).
-int dp_gather_acc(vaeb_ctx* c) {
-    if (!c->comm || !c->dp_shard) return 0;
-    const DpBucket bk = dp_bucket_all_runs(c);
-    if (int rc = nccl_ok(ncclGroupStart(), "ncclGroupStart")) return rc;
-    int rc = 0;
-    for (int j = 0; j < bk.nrun && !rc; ++j) {
-        const int64_t S = dp_shard_len(c, bk.n[j]);
-        float* t = c->acc + bk.lo[j];
-        if (S) rc = nccl_ok(ncclAllGather(t + c->rank * S, t, (size_t)S, ncclFloat, c->comm, c->s), "ncclAllGather");
-    }
-    const int re = nccl_ok(ncclGroupEnd(), "ncclGroupEnd");
-    if (rc) return rc;
-    if (re) return re;
-    HIP_TRY(hipStreamSynchronize(c->s));
-    return 0;
-}
-
-// after the dW2 (| dW6) launch: opt(stream, range) enqueues the optimizer over a range,
-// fix(stream, range) the bf16 shadow of other ranks' shards (fp32: nothing)
-template <class Opt, class Fix>
-int dp_bucket_a(vaeb_ctx* c, const Prof& pr, float* theta_out, Opt opt, Fix fix) {
-    if (pr.on || !c->dp_overlap) return 0;
-    HIP_TRY(hipEventRecord(c->dp_ev[0], c->s));
-    HIP_TRY(hipStreamWaitEvent(c->s2, c->dp_ev[0], 0));
-    if (int rc = dp_reduce_update(c, c->s2, dp_bucket_a_runs(c), theta_out, opt, fix, c->dp_ev[1])) return rc;
-    HIP_TRY(hipEventRecord(c->dp_ev[2], c->s2));
-    return 0;
-}
-
-// after the last weight-gradient launch (the SGVB slot written)
-template <class Opt, class Fix>
-int dp_bucket_b(vaeb_ctx* c, Prof& pr, int opt_mark, float* theta_out, Opt opt, Fix fix) {
-    if (pr.on || !c->dp_overlap)
-        return dp_reduce_update(c, c->s, dp_bucket_all_runs(c), theta_out, opt, fix, nullptr, pr.on ? &pr : nullptr,
-                                opt_mark);
-    HIP_TRY(hipStreamWaitEvent(c->s, c->dp_ev[1], 0));
-    if (int rc = dp_reduce_update(c, c->s, dp_bucket_b_runs(c), theta_out, opt, fix, nullptr)) return rc;
-    HIP_TRY(hipStreamWaitEvent(c->s, c->dp_ev[2], 0));
-    return 0;
-}
+#include "dp_buckets.inc"   // the data-parallel gradient buckets (both engines)
+#include "engine_f32.inc"   // the fp32 step engine
 
 // ------------------------------------------------------------------ the 16-bit engine
 // One host engine (engine_bf16.inc) over two device instantiations (h16_engines.hpp): bf16
@@ -1024,231 +331,9 @@ int bf_eval_chunk_dev(vaeb_ctx* c, const bf16_t* x, int rows, int64_t r0, int mo
 int h16_dp_opt(vaeb_ctx* c, int par, const DpRange& own) { return H16_CALL(h16_dp_opt, c, par, own); }
 int h16_dp_fix(vaeb_ctx* c, int par, const DpRange& fr) { return H16_CALL(h16_dp_fix, c, par, fr); }
 
-// One training step reading parameter arena `par` and writing arena par ^ 1.
-// One stream: P1 -> P23 -> P4 -> [P5 | dW2 (| dW6)] -> [P67 | dW1] -> [dW3 | dW45 + ELBO]
-// (bracketed groups share one grid, see hfuse.hpp); DP adds all-reduce -> Adagrad.
-// `prof` brackets every launch with timing events.
-// fresh: first step of an enqueued sequence (VAEB_EST_FVS in Philox mode draws the weight
-// sample here; later steps of the sequence read the one their predecessor's update wrote).
-// direct >= 0: the step's minibatch index given by the host (vaeb_update's single eager
-// step): the rows are addressed from the launch arguments, no order upload, no cursor.
+// One training step of the context's engine (engine_f32.inc enqueue_train_step_f32 for the arguments).
 int enqueue_train_step(vaeb_ctx* c, int par, bool prof, bool fresh = true, int direct = -1) {
-    if (is_bf16(c)) return bf_train_step(c, par, prof, direct);
-    Prof pr{c, prof};
-    if (prof) pr.reps = c->prof_reps;
-    const vaeb_config& g = c->c;
-    hipStream_t s = c->s;
-    // VAEB_EST_FVS: the step reads the weight sample theta~ written into the spare arena
-    // par ^ 1 (the loaded theta in arena par is never updated, as on the literal path)
-    const bool fvs = g.estimator == VAEB_EST_FVS;
-    const float* zin = (fvs && c->eps_mode == VAEB_EPS_HOST) ? c->fvzeta : nullptr;
-    if (fvs && (fresh || zin)) {
-        pr.mark(37);
-        REP(pr) hipLaunchKernelGGL(fvs_sample_kernel, dim3(kFvParts), dim3(256), 0, s, c->fvmu, c->fvsg,
-                                   c->theta2[par ^ 1], c->P, c->seed, c->step, zin);
-        CHECK_LAUNCH();
-    }
-    if (fvs) par ^= 1;
-    StepArgs a = make_args(c, par, g.B, g.estimator == VAEB_EST_FV ? MODE_EVAL : MODE_TRAIN, c->data, true);
-    if (direct >= 0) {
-        const int64_t row0 = (int64_t)direct * g.B_global + g.row_offset;
-        a.order = nullptr;
-        a.xbase = c->data + row0 * g.D;
-        a.batch_stride = 0;
-        a.row_base_mul = 0;
-        a.row_base_add = row0;
-    }
-    // literal FV: the (mu, sigma) update needs none of the step's data; with the folded
-    // latent block it rides enc_latent_kernel's extra grid rows (~256 blocks), else it is
-    // fv_kernel's launch
-    const bool fv_fold = g.estimator == VAEB_EST_FV && folded_latent(c, a);
-    int n_fv = kFvParts;
-    FvFold fvf{};
-    if (fv_fold) {
-        fvf = FvFold{c->fvmu, c->fvsg, c->fvam, c->fvas, c->fv_part, c->P, g.lr, g.adagrad_eps, cdiv(256, a.Mbp / 16)};
-        n_fv = fvf.rows * (a.Mbp / 16);
-        if (n_fv > kFvParts) return fail(VAEB_ERR_ARG, "internal: %d FV partials > %d", n_fv, kFvParts);
-    }
-    // the deferred dW2: the PREVIOUS step's dW2 (| dW6) rides this step's encoder launch --
-    // theta from the other arena, theta' into this step's (make_opt(par ^ 1)); this step's own
-    // dW2 is left pending for the next step (or a flush)
-    const bool w2d = dw2_deferred(c, a);
-    W2Launch w2{};
-    if (w2d) {
-        const W2Plan pl = w2_plan_for(c, a);
-        w2.width = pl.width;
-        w2.paired = pl.paired != 0;
-        if (int rc = w2_args(c, a, make_opt(c, par ^ 1, true, g.keep_grads != 0), 0, w2.w, w2.vec, pl.width)) return rc;
-        if (pl.width == 64 && !w2.vec) return fail(VAEB_ERR_ARG, "internal: 64-wide dW2 tiles need 16-byte accesses");
-        // (timeline build: the dW2 tiles stamp at logical ids 256 + tile of the encoder launch)
-        w2.w.dbg = c->dbg ? c->dbg + (size_t)c->dbg_slot * kDbgWG * 8 + 256 * 8 : nullptr;
-        w2.pend = c->w2pend;
-    }
-    if (int rc = enqueue_forward(c, a, pr, fvf, w2d ? &w2 : nullptr)) return rc;
-    ElboArgs e = base_elbo(c, a);
-    e.elbo_out = c->elbo_out; e.epoch = c->epoch; e.cursor = direct >= 0 ? nullptr : c->ictl; e.step = c->step;
-
-    if (g.estimator == VAEB_EST_FV) {
-        if (!fv_fold) {
-            pr.mark(10);
-            REP(pr) hipLaunchKernelGGL(fv_kernel, dim3(kFvParts), dim3(256), 0, s, c->fvmu, c->fvsg, c->fvam,
-                                       c->fvas, c->P, g.lr, g.adagrad_eps, 1, c->fv_part);
-            CHECK_LAUNCH();
-        }
-        pr.mark(11);
-        e.fv_part = c->fv_part; e.n_fv = n_fv;
-        e.data_mul = (double)g.B;
-        hipLaunchKernelGGL(elbo_kernel, dim3(1), dim3(256), 0, s, e);
-        CHECK_LAUNCH();
-        pr.mark(-1);
-        c->prof_n = pr.k;
-        return 0;
-    }
-    const bool dp = c->comm != nullptr;  // any communicator (also world 1) takes the all-reduce path
-    // FVS: the weight-gradient launches only store the data gradient at theta~
-    const OptArgs opt = make_opt(c, par, !dp && !fvs, dp || fvs || g.keep_grads != 0);
-    const int bo = gaussian(c) ? 6 : 5;
-    const bool gs = gaussian(c);
-    const OptArgs dopt = make_opt(c, par, true, false);
-    auto dp_opt = [&](hipStream_t st, const DpRange& r) -> int { return dp_opt_launch(c, st, dopt, r, e); };
-
-    // folded latent backward (Z <= 32, latent_bwd.hpp): the dhd launch also finishes dZ and
-    // [dMu | dLv]; dA3 is formed inside the dW3 workgroups of the last launch (with dW1)
-    const bool fold = fused_latent(c) && c->fold_bwd;
-    // P5 + dW2 (| dW6) = [hd|1]^T [dA2 (| dA6)] in one grid: both need only P4's outputs
-    a.dbg = next_dbg(c);
-    if (fold) {
-        WGroup g4 = make_group(c, c->hd, a.H, a.Me, 0, a.H, c->dA2, a.D, a.D, gs ? c->dA6 : nullptr, a.D, gs ? a.D : 0,
-                               a.Me, 4, bo + 4, gs ? 5 : -1, gs ? bo + 5 : -1);
-        const PDhdT<true> p5{a, a.Me, a.H, gs ? ((a.D + 3) & ~3) + a.D : a.D};
-        const PDhdT<false> p5s{a, a.Me, a.H, p5.K};
-        const int gx = cdiv(p5.M, 16), ntile = gx * cdiv(p5.N, 16);
-        WGradArgs w;
-        bool vec;
-        if (int rc = prep_wgrad(c, &g4, 1, opt, nullptr, a, ntile, w, vec, kWTJ_P5)) return rc;
-        // the dhd loaders' 16-byte form needs D % 4 == 0 and aligned dA2 / W2 too
-        vec = vec && dhd_vec(a);
-        DhdAux pend{nullptr};
-        if (w2d) {   // no dW2 tiles here: the next step's encoder launch (or a flush) runs them
-            w.total_wgs = ntile;
-            pend.pend = c->w2pend;
-        }
-        const dim3 grid(w.total_wgs);
-        const bool deep = cdiv(cdiv(p5.K, 16), 8) > 4;
-        pr.mark(w2d ? 43 : 39);
-        REP(pr) {
-            switch (ho_dz(c)) {
-                case 1: launch_dhd_dz<kWTJ_P5 / 16, 1>(s, grid, p5, p5s, w, ntile, gx, vec, deep, pend); break;
-                case 2: launch_dhd_dz<kWTJ_P5 / 16, 2>(s, grid, p5, p5s, w, ntile, gx, vec, deep, pend); break;
-                default: launch_dhd_dz<kWTJ_P5 / 16, 0>(s, grid, p5, p5s, w, ntile, gx, vec, deep, pend); break;
-            }
-        }
-        CHECK_LAUNCH();
-        if (w2d) c->w2_dirty = true;
-    } else {
-        WGroup g4 = make_group(c, c->hd, a.H, a.Me, 0, a.H, c->dA2, a.D, a.D, gs ? c->dA6 : nullptr, a.D, gs ? a.D : 0,
-                               a.Me, 4, bo + 4, gs ? 5 : -1, gs ? bo + 5 : -1);
-        const PDhdT<true> p5{a, a.Me, a.H, gs ? ((a.D + 3) & ~3) + a.D : a.D};
-        const PDhdT<false> p5s{a, a.Me, a.H, p5.K};
-        const int gx = cdiv(p5.M, 16), ntile = gx * cdiv(p5.N, 16);
-        WGradArgs w;
-        bool vec;
-        if (int rc = prep_wgrad(c, &g4, 1, opt, nullptr, a, ntile, w, vec, kWTJ_P5)) return rc;
-        vec = vec && dhd_vec(a);
-        const dim3 grid(w.total_wgs);
-        pr.mark(4);
-        REP(pr) if (cdiv(cdiv(p5.K, 16), 8) <= 4) {
-            if (vec) hipLaunchKernelGGL((tile_wgrad_kernel<1, 1, 8, 1, 4, PDhdT<true>, true, kWTJ_P5 / 16>), grid, dim3(512), 0, s, p5, w, ntile, gx);
-            else hipLaunchKernelGGL((tile_wgrad_kernel<1, 1, 8, 1, 4, PDhdT<false>, false, kWTJ_P5 / 16>), grid, dim3(512), 0, s, p5s, w, ntile, gx);
-        } else {
-            if (vec) hipLaunchKernelGGL((tile_wgrad_kernel<1, 1, 8, 1, 8, PDhdT<true>, true, kWTJ_P5 / 16>), grid, dim3(512), 0, s, p5, w, ntile, gx);
-            else hipLaunchKernelGGL((tile_wgrad_kernel<1, 1, 8, 1, 8, PDhdT<false>, false, kWTJ_P5 / 16>), grid, dim3(512), 0, s, p5s, w, ntile, gx);
-        }
-        CHECK_LAUNCH();
-    }
-    auto no_fix = [](hipStream_t, const DpRange&) -> int { return 0; };
-    if (dp) if (int rc = dp_bucket_a(c, pr, dopt.theta_out, dp_opt, no_fix)) return rc;
-    // P67 (+ dW1 = [z|1]^T dA1 on the fused path): both need only P5's output
-    if (!fold) {
-        a.dbg = next_dbg(c);
-        WGroup g3 = make_group(c, c->z, a.Z, a.Me, 0, a.Z, c->dA1, a.H, a.H, nullptr, 0, 0, a.Me, 3, bo + 3, -1, -1);
-        if (fused_latent(c)) {
-            const int nrow = a.Mbp / 16 * std::max(1, std::min(kDzSplit, cdiv(a.H, 16)));
-            WGradArgs w;
-            bool vec;
-            if (int rc = prep_wgrad(c, &g3, 1, opt, nullptr, a, nrow, w, vec, kWTJ_P67)) return rc;
-            const dim3 grid(w.total_wgs);
-            pr.mark(13);
-            REP(pr) if (a.Z <= 16) {
-                if (vec) hipLaunchKernelGGL((dz_dh_wgrad_kernel<1, true, kWTJ_P67 / 16>), grid, dim3(512), 0, s, a, w, nrow);
-                else hipLaunchKernelGGL((dz_dh_wgrad_kernel<1, false, kWTJ_P67 / 16>), grid, dim3(512), 0, s, a, w, nrow);
-            } else {
-                if (vec) hipLaunchKernelGGL((dz_dh_wgrad_kernel<2, true, kWTJ_P67 / 16>), grid, dim3(512), 0, s, a, w, nrow);
-                else hipLaunchKernelGGL((dz_dh_wgrad_kernel<2, false, kWTJ_P67 / 16>), grid, dim3(512), 0, s, a, w, nrow);
-            }
-            CHECK_LAUNCH();
-        } else {
-            pr.mark(15);
-            REP(pr) if (int rc = launch_wgrad(c, s, &g3, 1, opt, nullptr, a)) return rc;
-            a.dbg = next_dbg(c);
-            pr.mark(5);
-            REP(pr) launch_tile<1, 1, 4, 1, 8>(s, PDz{a, a.Me, a.Z, a.H});
-            CHECK_LAUNCH();
-            a.dbg = next_dbg(c);
-            pr.mark(6);
-            REP(pr) launch_tile<1, 4, 1, 1, 8>(s, PDh{a, a.Mbp, a.H, 2 * a.Z});
-            CHECK_LAUNCH();
-        }
-    }
-    // dW3 = [X|1]^T dA3 and dW4|dW5 = [h|1]^T [dMu|dLv] (+ dW1 = [z|1]^T dA1 when the latent
-    // backward is folded: dA3 is then formed in the dW3 workgroups), plus the ELBO workgroup
-    {
-        WGroup g12[3] = {
-            make_group(c, nullptr, a.D, a.Mb, 1, a.D, c->dA3, a.H, a.H, nullptr, 0, 0, a.Mbp, 0, bo + 0, -1, -1),
-            make_group(c, c->h, a.H, a.Mbp, 0, a.H, c->dMuLv, 2 * a.Z, a.Z, c->dMuLv + a.Z, 2 * a.Z, a.Z, a.Mbp, 1,
-                       bo + 1, 2, bo + 2),
-            make_group(c, c->z, a.Z, a.Me, 0, a.Z, c->dA1, a.H, a.H, nullptr, 0, 0, a.Me, 3, bo + 3, -1, -1)};
-        ElboArgs e1 = e;
-        if (dp || fvs) { e1.dp_slot = c->grad + c->P; e1.elbo_out = nullptr; e1.cursor = nullptr; e1.step = nullptr; }
-        a.dbg = next_dbg(c);
-        if (fold) {
-            Da3Src d3{c->dMuLv, a.W4, a.W5, c->h, c->dA3, a.Z, a.H, a.Mb, a.Mbp, LatRed{}};
-            if (ho_dz(c) == 2) {
-                // the deferred latent backward: ceil(Z / 8) column groups per 16-row block
-                LatRed& r = d3.red;
-                r.slab = c->slab_dz; r.mu = c->mu; r.lv = c->lv; r.eps = c->eps; r.z = c->z;
-                r.dZ = c->dZ; r.dml = c->dMuLv; r.cnt = c->cnt_dz; r.guard = c->blk + kBlkFxErr;
-                // (Z % 4 == 0: groups of a multiple of 4 latents, so VAEB_LAT_ST4 reducers can
-                // publish whole 16-byte runs; MNIST-20: 8, 8, 4)
-                r.ngrp = cdiv(a.Z, 8); r.zg = cdiv(a.Z, r.ngrp);
-                if (a.Z % 4 == 0) { r.zg = (r.zg + 3) & ~3; r.ngrp = cdiv(a.Z, r.zg); }
-                r.nred = (a.Mbp / 16) * r.ngrp;
-                r.nctH = cdiv(a.H, 16); r.L = a.L; r.est = a.est; r.Mb = a.Mb; r.Mbp = a.Mbp; r.Z = a.Z; r.sc = a.sc;
-            }
-            pr.mark(40);
-            REP(pr) if (int rc = launch_wgrad(c, s, g12, 3, opt, &e1, a, &d3)) return rc;
-        } else {
-            pr.mark(7);
-            REP(pr) if (int rc = launch_wgrad(c, s, g12, 2, opt, &e1, a)) return rc;
-        }
-    }
-    if (fvs) {   // Adagrad on (mu_theta, sigma_theta), then the step's SGVB / B and cursor++
-        pr.mark(38);
-        REP(pr) hipLaunchKernelGGL(fvs_update_kernel, dim3(kFvParts), dim3(256), 0, s, c->fvmu, c->fvsg, c->fvam,
-                                   c->fvas, (const float*)c->grad, c->P, (float)g.B, g.lr, g.adagrad_eps, c->seed,
-                                   (const int64_t*)c->step, zin, c->fv_part, zin ? nullptr : c->theta2[par]);
-        CHECK_LAUNCH();
-        pr.mark(11);
-        e.fv_part = c->fv_part; e.n_fv = kFvParts;
-        e.data_mul = (double)g.B;
-        e.est = VAEB_EST_FV;   // SGVB = B (sum log p + sum KL) + thetaPrior (VAEB.py:364)
-        hipLaunchKernelGGL(elbo_kernel, dim3(1), dim3(256), 0, s, e);
-        CHECK_LAUNCH();
-    }
-    if (dp) if (int rc = dp_bucket_b(c, pr, 9, dopt.theta_out, dp_opt, no_fix)) return rc;
-    pr.mark(-1);
-    c->prof_n = pr.k;
-    return 0;
+    return is_bf16(c) ? bf_train_step(c, par, prof, direct) : enqueue_train_step_f32(c, par, prof, fresh, direct);
 }
 
 bool flips(const vaeb_ctx* c) { return c->c.estimator != VAEB_EST_FV && c->c.estimator != VAEB_EST_FVS; }
@@ -1339,18 +424,6 @@ int run_steps(vaeb_ctx* c, int n) {
     }
     for (int i = 0; i < n; ++i)
         if (int rc = step_eager(c)) return rc;
-    return 0;
-}
-
-// The order upload update_many held back for its eager first step (vaeb_ctx::order_pending):
-// launched right after that step's first kernel, or after the step where no launch site
-// takes it.  The eager step addresses its rows from its launch arguments and reads neither the
-// order nor the cursor, so the upload may run between its launches.
-int order_hook(vaeb_ctx* c) {
-    if (!c->order_pending) return 0;
-    c->order_pending = false;
-    hipLaunchKernelGGL(set_order_kernel, dim3(1), dim3(256), 0, c->s, c->ictl, c->order_pend);
-    CHECK_LAUNCH();
     return 0;
 }
 
@@ -1841,30 +914,6 @@ static int eval_arena(vaeb_ctx* c, int* epar) {
     return 0;
 }
 
-// One fp32 chunk: `rows` device rows at x = global rows [r0, r0 + rows).  MODE_EVAL adds
-// the chunk's SGVB into eval_acc; MODE_RECON copies the decoder means to out_y (host).
-static int eval_chunk_f32(vaeb_ctx* c, int epar, const float* x, int rows, int64_t r0, int mode, float* out_y,
-                          float* out_lv = nullptr) {
-    const vaeb_config& g = c->c;
-    StepArgs a = make_args(c, epar, rows, mode, x, false);
-    a.row_base_add = r0;
-    a.eps_in = c->eps_in ? c->eps_in + r0 * g.Z : nullptr;
-    a.eps_in_ld = c->eps_rows;
-    Prof pr{c, false};
-    if (int rc = enqueue_forward(c, a, pr)) return rc;
-    if (mode == MODE_RECON) {
-        HIP_TRY(hipMemcpyAsync(out_y, c->y, sizeof(float) * (size_t)rows * g.D, hipMemcpyDeviceToHost, c->s));
-        if (out_lv)
-            HIP_TRY(hipMemcpyAsync(out_lv, c->dA6, sizeof(float) * (size_t)rows * g.D, hipMemcpyDeviceToHost, c->s));
-    } else {
-        ElboArgs e = base_elbo(c, a);
-        e.eval_acc = c->eval_acc;
-        hipLaunchKernelGGL(elbo_kernel, dim3(1), dim3(256), 0, c->s, e);
-        CHECK_LAUNCH();
-    }
-    return 0;
-}
-
 // eval_acc[0] on the host, after an optional all-reduce of it over the ranks: the call's
 // one stream synchronisation.
 static int eval_acc_read(vaeb_ctx* c, bool allreduce, double* out) {
@@ -2201,28 +1250,6 @@ int vaeb_decode(vaeb_ctx* c, const float* z, int64_t n, float* out_mu, float* ou
 }
 
 // ------------------------------------------------------------------ encoder outputs, IWAE bound
-// The encoder and heads of one fp32 chunk (rows at x = global rows [r0, r0 + rows)): c->mu and
-// c->lv hold it afterwards (VAEB.py:245-251).  The forward's own launches with zero noise and
-// one plane; what they also write (eps, z, hd plane 0, the KL partials) is scratch here.
-static int encode_chunk_f32(vaeb_ctx* c, int epar, const float* x, int rows, int64_t r0, StepArgs* out) {
-    StepArgs a = make_args(c, epar, rows, MODE_EVAL, x, false);
-    a.L = 1; a.Me = a.Mbp;
-    a.est = EST_LB;
-    a.eps_mode = 2;
-    a.row_base_add = r0;
-    launch_bigk<1>(c->s, PEnc{a, nullptr, a.Mbp, a.H, a.D});
-    CHECK_LAUNCH();
-    if (fused_latent(c)) {
-        if (a.Z <= 16) hipLaunchKernelGGL(heads_dechid_kernel<1>, dim3(a.Mbp / 16), dim3(512), 0, c->s, a);
-        else hipLaunchKernelGGL(heads_dechid_kernel<2>, dim3(a.Mbp / 16), dim3(512), 0, c->s, a);
-    } else {
-        launch_tile<1, 1, 4, 2, 8>(c->s, PHeads{a, a.Mbp, a.Z, a.H});
-    }
-    CHECK_LAUNCH();
-    if (out) *out = a;
-    return 0;
-}
-
 int vaeb_encode(vaeb_ctx* c, const float* x, int64_t n, float* out_mu, float* out_lv) {
     if (!c || !x || n <= 0) return fail(VAEB_ERR_ARG, "bad arguments");
     if (is_bf16(c)) return fail(VAEB_ERR_ARG, "vaeb_encode is served by fp32 contexts");
@@ -2239,46 +1266,6 @@ int vaeb_encode(vaeb_ctx* c, const float* x, int64_t n, float* out_mu, float* ou
         if (out_lv) HIP_TRY(hipMemcpyAsync(out_lv + r0 * g.Z, c->lv, nb, hipMemcpyDeviceToHost, c->s));
     }
     HIP_TRY(hipStreamSynchronize(c->s));
-    return 0;
-}
-
-// IW_K of one chunk (iwae.hpp): `rows` device rows at x = global rows [r0, r0 + rows); eps_k0:
-// host eps mode, sample 0's noise row of the chunk's row 0 (sample k is eps_ld rows further).
-// Adds the chunk's sum to eval_acc[0]; the row values go to out_rows (host) when given.
-static int iw_chunk_f32(vaeb_ctx* c, int epar, const float* x, int rows, int64_t r0, int K, const float* eps_k0,
-                        int64_t eps_ld, float* out_rows) {
-    const vaeb_config& g = c->c;
-    StepArgs a;
-    if (int rc = encode_chunk_f32(c, epar, x, rows, r0, &a)) return rc;
-    const int64_t planes = (int64_t)c->cap * g.L;   // rows of z / hd / lp_part
-    IwArgs w{};
-    w.Z = g.Z; w.Mb = rows; w.Mbp = a.Mbp; w.nctD = a.nctD;
-    w.K = K; w.logK = (float)std::log((double)K);
-    w.row0 = r0;
-    w.eps_mode = c->eps_mode == VAEB_EPS_HOST ? 1 : 0;
-    w.seed = c->seed; w.step = c->step;
-    w.eps_in = eps_k0; w.eps_ld = eps_ld;
-    w.mu = c->mu; w.lv = c->lv; w.z = c->z; w.lp_part = c->lp_part;
-    w.lat = c->iw; w.ms = c->iw + planes; w.rows = w.ms + 2 * (int64_t)c->cap;
-    const int smax = (int)std::min<int64_t>(planes / a.Mbp, K);
-    for (int k0 = 0; k0 < K; k0 += smax) {
-        const int S = std::min(smax, K - k0);
-        w.k0 = k0; w.S = S;
-        hipLaunchKernelGGL(iw_sample_kernel, dim3((unsigned)(S * (a.Mbp / 16))), dim3(256), 0, c->s, w);
-        CHECK_LAUNCH();
-        StepArgs d = a;
-        d.L = S; d.Me = S * a.Mbp;
-        launch_tile<1, 4, 1, 1, 8>(c->s, PDecHid{d, d.Me, d.H, d.Z});
-        CHECK_LAUNCH();
-        if (gaussian(c)) launch_bigk<2>(c->s, PDecOut{d, nullptr, d.Me, d.D, d.H});
-        else launch_bigk<1>(c->s, PDecOut{d, nullptr, d.Me, d.D, d.H});
-        CHECK_LAUNCH();
-        hipLaunchKernelGGL(iw_lse_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, c->s, w);
-        CHECK_LAUNCH();
-    }
-    hipLaunchKernelGGL(iw_sum_kernel, dim3(1), dim3(256), 0, c->s, w.rows, (int64_t)rows, c->eval_acc);
-    CHECK_LAUNCH();
-    if (out_rows) HIP_TRY(hipMemcpyAsync(out_rows, w.rows, sizeof(float) * (size_t)rows, hipMemcpyDeviceToHost, c->s));
     return 0;
 }
 
@@ -2578,8 +1565,7 @@ int vaeb_dw2_plan(const vaeb_config* cfg, int32_t* out_width, int32_t* out_paire
     StepArgs a{};
     a.D = cfg->D; a.H = cfg->H; a.Z = cfg->Z;
     a.Mb = cfg->B; a.Mbp = r16(cfg->B);
-    int ct = 1;
-    enc_form(&c, a, FvFold{}, nullptr, &ct, nullptr);
+    const int ct = enc_form(&c, a).ct;
     const W2Plan pl = w2_plan_for(&c, a);
     const int rows = a.H + 1, cols = (gaussian(&c) ? 2 : 1) * a.D, n = pl.tiles_i * pl.tiles_j;
     if (out_width) *out_width = pl.width;

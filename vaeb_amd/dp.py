@@ -135,7 +135,7 @@ def comm_setup(ctx, dist, rank, world):
 
 
 def arena_runs(offsets, P, gaussian=False):
-    """The three runs the DP optimizer partitions the parameter arena into (vaeb_hip.hip
+    """The three runs the DP optimizer partitions the parameter arena into (dp_buckets.inc
     dp_bucket_all_runs): B0 = [0, W2), A = [W2, b3) (W2 | W6), B1 = [b3, P); `offsets` are
     the arena offsets in reference order (W3 W4 W5 W1 W2 [W6] b3 ...)."""
     bo = 6 if gaussian else 5
@@ -143,12 +143,12 @@ def arena_runs(offsets, P, gaussian=False):
 
 
 def shard_len(n, world, sharded=True):
-    """Elements per rank of a run of n (vaeb_hip.hip dp_shard_len): 64-aligned floor(n / world)."""
+    """Elements per rank of a run of n (dp_buckets.inc dp_shard_len): 64-aligned floor(n / world)."""
     return (n // world) & ~63 if sharded else 0
 
 
 def shard_plan(runs, world, rank, sharded=True):
-    """Host mirror of the sharded optimizer's index plan (vaeb_hip.hip dp_reduce_update,
+    """Host mirror of the sharded optimizer's index plan (dp_buckets.inc dp_reduce_update,
     dp_opt_range, dp_foreign_range), for tests and the cost model.  Per run (lo, n):
     reduce-scatter of world * S elements (this rank's shard [lo + rank S, +S)), all-reduce of
     the remainder [lo + world S, lo + n); the optimizer updates the shard and the remainder;
