@@ -21,6 +21,9 @@ CASES = [
     ("deep_odd", dict(Dobs=37, Denc=(29, 17), Dz=5, Ddec=(13, 21), otype="binary", s2=2.0), 23),
     ("deep_cont_sigmoid", dict(Dobs=48, Denc=(20,), Dz=4, Ddec=(18, 11), otype="cont", act="sigmoid"), 30),
     ("relu", dict(Dobs=64, Denc=(32,), Dz=8, Ddec=(32,), otype="binary", act="relu"), 32),
+    # K > 512 takes the deep main loop (8 chunks in flight): the weight gradients' K is the batch,
+    # the continuous output layer's K the last decoder width
+    ("deep_k_cont", dict(Dobs=40, Denc=(24,), Dz=4, Ddec=(520,), otype="cont"), 528),
 ]
 
 
