@@ -229,6 +229,15 @@ int vaeb_get_activation(vaeb_ctx* ctx, const char* name, float* out, int64_t n);
 #define VAEB_AE_MAX_LAYERS 8
 enum vaeb_ae_otype { VAEB_AE_BINARY = 0, VAEB_AE_CONT = 1 };   /* ae.py:58 / :65 */
 enum vaeb_act      { VAEB_ACT_TANH = 0, VAEB_ACT_SIGMOID = 1, VAEB_ACT_RELU = 2 };   /* f, ae.py:41 */
+/* The latent layer.  POINT: the reference's degenerate VAE above.  GAUSS (extension: a deep VAE
+ * on the same layer stack), on the rows X = Xtr[idx], M = |idx|, H the last encoder activation,
+ * one sample per row:
+ *   mu = H Wzmu + bzmu,  lv = H Wzlv + bzlv,  z = mu + exp(lv / 2) eps,  the decoder is fed z,
+ *   negKL = 1/2 sum_{m,j} (1 + lv - mu^2 - exp(lv))     (replaces the N(0, 1) prior on Z),
+ *   f = loglik + negKL + N(0, s2) prior on theta        (maximised by the same AdaGrad),
+ * and train(idx) returns (loglik + negKL) / M.  In theta, [Wz, bz] become
+ * [Wzmu, Wzlv, bzmu, bzlv] (the cont output's convention); everything else keeps its place. */
+enum vaeb_ae_latent { VAEB_AE_LATENT_POINT = 0, VAEB_AE_LATENT_GAUSS = 1 };
 
 typedef struct vaeb_ae_config {
     int32_t Dobs;                         /* observation size                                */
@@ -243,7 +252,8 @@ typedef struct vaeb_ae_config {
     float   eta;                          /* AdaGrad learning rate (infalg.py:144)           */
     int32_t max_batch;                    /* largest idx list / predict chunk                */
     int32_t device;
-    int32_t reserved[4];
+    int32_t latent;                       /* enum vaeb_ae_latent (0: the point latent)       */
+    int32_t reserved[3];
 } vaeb_ae_config;
 
 typedef struct vaeb_ae vaeb_ae;
@@ -264,6 +274,32 @@ int vaeb_ae_train_many(vaeb_ae* ae, const int32_t* idx, int32_t n, int32_t batch
 int vaeb_ae_reconstruct(vaeb_ae* ae, const float* x, int64_t n, float* out);   /* ae.py:92-98  */
 int vaeb_ae_encode(vaeb_ae* ae, const float* x, int64_t n, float* z_out);      /* ae.py:101-107 */
 int vaeb_ae_decode(vaeb_ae* ae, const float* z, int64_t n, float* out);        /* ae.py:110-116 */
+
+/* VAEB_AE_LATENT_GAUSS contexts only (VAEB_ERR_ARG on a point-latent context).  On such a
+ * context vaeb_ae_encode returns mu, vaeb_ae_reconstruct decodes z = mu and vaeb_ae_decode is
+ * unchanged.
+ *
+ * Noise, with the conventions of "Noise" above (enum vaeb_eps_mode; default PHILOX, seed 0,
+ * step 0).  PHILOX: eps[m][j] is the draw at the counter (c0, c1 = j, c2, c3) under the seed:
+ *   training    c0 = idx[m], the dataset row (so a row's draw does not depend on the batch it
+ *               falls in); c2, c3 = the step.  Each train step draws at the context's step and
+ *               advances it by one (vaeb_ae_train_many: one per slice).
+ *   evaluation  (vaeb_ae_encode_dist's z, vaeb_ae_elbo) c0 = the row's index in the x passed to
+ *               the call; c2, c3 = step ^ 1 << 63 (stream 0), at the current step, which stays.
+ * HOST: the caller pushes eps [rows x Dz] in the row order of the next call (vaeb_ae_train_many:
+ * of the whole idx list); a call that draws noise for another row count is VAEB_ERR_STATE.  The
+ * pushed eps stays until the next push. */
+int vaeb_ae_set_eps_mode(vaeb_ae* ae, int32_t mode, uint64_t seed);
+int vaeb_ae_push_eps(vaeb_ae* ae, const float* eps, int64_t rows);
+int vaeb_ae_set_step(vaeb_ae* ae, int64_t step);    /* Philox step counter */
+int vaeb_ae_get_step(vaeb_ae* ae, int64_t* step);
+/* Encoder outputs for host x [n x Dobs]: mu, log-variance and one evaluation-noise sample
+ * z = mu + exp(lv / 2) eps, each [n x Dz]; any of the three may be NULL (no noise is drawn
+ * without out_z). */
+int vaeb_ae_encode_dist(vaeb_ae* ae, const float* x, int64_t n, float* out_mu, float* out_lv, float* out_z);
+/* Forward-only sum of loglik + negKL over n rows of host x with evaluation noise, in max_batch
+ * chunks (no theta prior).  Changes no parameter, accumulator or step. */
+int vaeb_ae_elbo(vaeb_ae* ae, const float* x, int64_t n, double* out_sum);
 
 #ifdef __cplusplus
 }

@@ -37,6 +37,8 @@ EXPORTS = [
     "vaeb_ae_create", "vaeb_ae_destroy", "vaeb_ae_num_params", "vaeb_ae_set_data", "vaeb_ae_set_params",
     "vaeb_ae_get_params", "vaeb_ae_set_adagrad_state", "vaeb_ae_get_adagrad_state", "vaeb_ae_train",
     "vaeb_ae_train_many", "vaeb_ae_reconstruct", "vaeb_ae_encode", "vaeb_ae_decode",
+    "vaeb_ae_set_eps_mode", "vaeb_ae_push_eps", "vaeb_ae_set_step", "vaeb_ae_get_step", "vaeb_ae_encode_dist",
+    "vaeb_ae_elbo",
 ]
 DIAG_EXPORTS = ["vaeb_profile_steps", "vaeb_kernel_name", "vaeb_debug_timeline", "vaeb_test_gemm_bf16",
                 "vaeb_bench_gemm_bf16", "vaeb_graph_status", "vaeb_comm_info", "vaeb_time_update_many", "vaeb_busy",
@@ -44,6 +46,7 @@ DIAG_EXPORTS = ["vaeb_profile_steps", "vaeb_kernel_name", "vaeb_debug_timeline",
 GRAPH_MODES = {0: "off", 1: "not_captured", 2: "replay", 3: "eager_fallback"}
 AE_MAX_LAYERS = 8
 AE_BINARY, AE_CONT = 0, 1
+AE_LATENT = {"point": 0, "gauss": 1}
 ACT = {"tanh": 0, "sigmoid": 1, "relu": 2}
 
 
@@ -63,7 +66,8 @@ class AEConfigC(ctypes.Structure):
         ("Dobs", ctypes.c_int32), ("n_enc", ctypes.c_int32), ("Denc", ctypes.c_int32 * 8),
         ("Dz", ctypes.c_int32), ("n_dec", ctypes.c_int32), ("Ddec", ctypes.c_int32 * 8),
         ("otype", ctypes.c_int32), ("act", ctypes.c_int32), ("s2", ctypes.c_float), ("eta", ctypes.c_float),
-        ("max_batch", ctypes.c_int32), ("device", ctypes.c_int32), ("reserved", ctypes.c_int32 * 4),
+        ("max_batch", ctypes.c_int32), ("device", ctypes.c_int32), ("latent", ctypes.c_int32),
+        ("reserved", ctypes.c_int32 * 3),
     ]
 
 
@@ -164,6 +168,12 @@ def load():
         "vaeb_ae_reconstruct": ([_P, _F, _I64, _F], ctypes.c_int),
         "vaeb_ae_encode": ([_P, _F, _I64, _F], ctypes.c_int),
         "vaeb_ae_decode": ([_P, _F, _I64, _F], ctypes.c_int),
+        "vaeb_ae_set_eps_mode": ([_P, ctypes.c_int32, ctypes.c_uint64], ctypes.c_int),
+        "vaeb_ae_push_eps": ([_P, _F, _I64], ctypes.c_int),
+        "vaeb_ae_set_step": ([_P, _I64], ctypes.c_int),
+        "vaeb_ae_get_step": ([_P, ctypes.POINTER(_I64)], ctypes.c_int),
+        "vaeb_ae_encode_dist": ([_P, _F, _I64, _F, _F, _F], ctypes.c_int),
+        "vaeb_ae_elbo": ([_P, _F, _I64, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -533,10 +543,11 @@ class Context:
 
 
 class AEContext:
-    """One degenerate-vae autoencoder (vaeb_ae_*) on one GPU."""
+    """One degenerate-vae autoencoder (vaeb_ae_*) on one GPU; latent="gauss": the deep VAE on
+    the same layer stack (include/vaeb_hip.h enum vaeb_ae_latent)."""
 
     def __init__(self, Dobs, Denc, Dz, Ddec, otype="binary", act="tanh", s2=1.0, eta=0.01, max_batch=100,
-                 device=0):
+                 device=0, latent="point"):
         self.lib = load()
         c = AEConfigC()
         c.Dobs, c.Dz = int(Dobs), int(Dz)
@@ -552,6 +563,9 @@ class AEContext:
         c.act = ACT[act]
         c.s2, c.eta = float(s2), float(eta)
         c.max_batch, c.device = int(max_batch), int(device)
+        if latent not in AE_LATENT:
+            raise VaebError(f"latent {latent!r} not supported (point | gauss)")
+        c.latent = AE_LATENT[latent]
         self.cfg = c
         self.Dobs, self.Dz = c.Dobs, c.Dz
         self.h = _P()
@@ -622,3 +636,36 @@ class AEContext:
 
     def decode(self, z):
         return self._predict(self.lib.vaeb_ae_decode, z, self.Dobs)
+
+    # ---- Gaussian latent (latent="gauss") ----
+    def set_eps_mode(self, mode, seed=0):
+        check(self.lib.vaeb_ae_set_eps_mode(self.h, int(mode), int(seed)))
+
+    def push_eps(self, eps):
+        """Host eps mode: eps [rows x Dz] in the row order of the next call."""
+        eps = np.ascontiguousarray(eps, np.float32).reshape(-1, self.Dz)
+        check(self.lib.vaeb_ae_push_eps(self.h, fptr(eps), eps.shape[0]))
+
+    def set_step(self, step):
+        check(self.lib.vaeb_ae_set_step(self.h, int(step)))
+
+    def get_step(self):
+        n = _I64()
+        check(self.lib.vaeb_ae_get_step(self.h, ctypes.byref(n)))
+        return n.value
+
+    def encode_dist(self, x, mu=True, log_var=True, z=True):
+        """(mu, log_var, z) of the encoder at x [n x Dobs], each [n x Dz]; z is one
+        evaluation-noise sample; an output switched off is None."""
+        x = np.ascontiguousarray(x, np.float32)
+        outs = [np.empty((x.shape[0], self.Dz), np.float32) if want else None for want in (mu, log_var, z)]
+        check(self.lib.vaeb_ae_encode_dist(self.h, fptr(x), x.shape[0],
+                                           *[fptr(o) if o is not None else None for o in outs]))
+        return tuple(outs)
+
+    def elbo(self, x):
+        """Sum of loglik - KL over the rows of x with evaluation noise (forward only)."""
+        x = np.ascontiguousarray(x, np.float32)
+        out = ctypes.c_double()
+        check(self.lib.vaeb_ae_elbo(self.h, fptr(x), x.shape[0], ctypes.byref(out)))
+        return out.value

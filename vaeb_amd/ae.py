@@ -8,6 +8,10 @@ All compute runs in libvaeb_hip.so (vaeb_ae_*, vaeb_amd/csrc/ae_mlp.hpp); there 
 fallback.  Initialisation draws every weight and bias from the GLOBAL numpy RNG in the
 reference's construction order (mlp.py:36-49), so `numpy.random.seed(s)` before
 ConstructAE reproduces the reference's theta_0.
+
+`ConstructVAE` (extension) is the same constructor with a Gaussian latent: mu and log-variance
+heads, z = mu + exp(lv / 2) eps with device Philox noise, and train(idx) returning
+(loglik - KL) / len(idx) (include/vaeb_hip.h enum vaeb_ae_latent).
 """
 from __future__ import annotations
 
@@ -31,12 +35,18 @@ def _values(X):
     return np.asarray(X.get_value() if hasattr(X, "get_value") else X, np.float32)
 
 
-def param_shapes(Dobs, Denc, Dz, Ddec, otype):
-    """theta order of ae.py:51,56,64,72."""
+def param_shapes(Dobs, Denc, Dz, Ddec, otype, latent="point"):
+    """theta order of ae.py:51,56,64,72; latent="gauss": [Wz, bz] become
+    [Wzmu, Wzlv, bzmu, bzlv] (the cont output's convention)."""
     d_in = [Dobs] + list(Denc)
     shp = [(f"W{i}", (d_in[i], d_in[i + 1])) for i in range(len(Denc))]
     shp += [(f"b{i}", (Denc[i],)) for i in range(len(Denc))]
-    shp += [("Wz", (Denc[-1], Dz)), ("bz", (Dz,))]
+    if latent == "gauss":
+        shp += [("Wzmu", (Denc[-1], Dz)), ("Wzlv", (Denc[-1], Dz)), ("bzmu", (Dz,)), ("bzlv", (Dz,))]
+    elif latent == "point":
+        shp += [("Wz", (Denc[-1], Dz)), ("bz", (Dz,))]
+    else:
+        raise ValueError(f"latent {latent!r} not supported (point | gauss)")
     d_dec = [Dz] + list(Ddec)
     shp += [(f"W{i}", (d_dec[i], d_dec[i + 1])) for i in range(len(Ddec))]
     shp += [(f"b{i}", (Ddec[i],)) for i in range(len(Ddec))]
@@ -82,21 +92,20 @@ class _AccArena:
         self.ctx.set_adagrad_state(flat)
 
 
-def ConstructAE(Xtr, Denc=(500,), Dz=20, Ddec=(500,), f="tanh", s2=1.0, inf=None, otype="binary",
-                max_batch=None, device=0):
-    """ae.py:41-117.  Returns (train, reconstruct, encode, decode, theta)."""
+def _construct(latent, Xtr, Denc, Dz, Ddec, f, s2, inf, otype, max_batch, device):
+    """The shared body of ConstructAE / ConstructVAE; returns (ctx, theta)."""
     if otype not in ("binary", "cont"):
         raise ValueError("otype currently only supports binary.")   # ae.py:74-75 (and cont)
     inf = inf if inf is not None else AdaGrad(0.01)
     Xtr = _values(Xtr)
     Denc, Ddec = list(Denc), list(Ddec)
     Dobs = Xtr.shape[1]
-    shapes = param_shapes(Dobs, Denc, Dz, Ddec, otype)
+    shapes = param_shapes(Dobs, Denc, Dz, Ddec, otype, latent)
     # mlp.WeightMatrix / BiasVector: N(0, 0.01) from the global RNG, construction order
     theta0 = [np.random.normal(0.0, 0.01, size=s).astype(np.float32) for _, s in shapes]
     mb = int(max_batch) if max_batch else max(100, min(4096, Xtr.shape[0]))
     ctx = _lib.AEContext(Dobs, Denc, Dz, Ddec, otype=otype, act=_act_name(f), s2=s2, eta=inf.eta, max_batch=mb,
-                         device=device)
+                         device=device, latent=latent)
     ctx.set_data(Xtr)
     ctx.set_params(np.concatenate([t.ravel() for t in theta0]))
     offs = np.cumsum([0] + [int(np.prod(s)) for _, s in shapes])
@@ -105,11 +114,36 @@ def ConstructAE(Xtr, Denc=(500,), Dz=20, Ddec=(500,), f="tanh", s2=1.0, inf=None
     arena = _AccArena(ctx)
     updates = inf.construct(arena, theta)
     bind_updates(arena, theta, updates)
+    return ctx, theta
+
+
+def ConstructAE(Xtr, Denc=(500,), Dz=20, Ddec=(500,), f="tanh", s2=1.0, inf=None, otype="binary",
+                max_batch=None, device=0):
+    """ae.py:41-117.  Returns (train, reconstruct, encode, decode, theta)."""
+    ctx, theta = _construct("point", Xtr, Denc, Dz, Ddec, f, s2, inf, otype, max_batch, device)
 
     def train(idx):
         return ctx.train(np.asarray(idx, np.int32))
 
     train.ctx = ctx
+    return train, ctx.reconstruct, ctx.encode, ctx.decode, theta
+
+
+def ConstructVAE(Xtr, Denc=(500,), Dz=20, Ddec=(500,), f="tanh", s2=1.0, inf=None, otype="binary", seed=10,
+                 max_batch=None, device=0):
+    """ConstructAE with a Gaussian latent: the same five return values, theta in the order
+    [..., Wzmu, Wzlv, bzmu, bzlv, ...].  train(idx) takes one AdaGrad step on the ELBO of the
+    rows Xtr[idx] (one Philox draw per row and latent, keyed by `seed`, the dataset row and the
+    step) and returns (loglik - KL) / len(idx); encode(X) is mu, reconstruct(X) decodes z = mu.
+    train.ctx is the engine context; train.elbo(X) the forward-only sum of loglik - KL."""
+    ctx, theta = _construct("gauss", Xtr, Denc, Dz, Ddec, f, s2, inf, otype, max_batch, device)
+    ctx.set_eps_mode(_lib.EPS_PHILOX, seed)
+
+    def train(idx):
+        return ctx.train(np.asarray(idx, np.int32))
+
+    train.ctx = ctx
+    train.elbo = lambda X: ctx.elbo(_values(X))
     return train, ctx.reconstruct, ctx.encode, ctx.decode, theta
 
 

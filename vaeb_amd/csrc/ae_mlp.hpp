@@ -11,6 +11,11 @@
 //                         fused with the output deltas dlogjoint/da     PAeFwd (mode OUT_*)
 //   backward, per layer:  din = (dout W^T) * f'(h)      PAeBwd (mode DACT)
 //                         dZ  = dout W^T - Z            PAeBwd (mode ZPRIOR: N(0,1) prior on Z)
+//   Gaussian latent (VAEB_AE_LATENT_GAUSS; replaces the linear Z layer and its prior):
+//                         mu = H Wzmu + bzmu, lv = H Wzlv + bzlv, z = mu + exp(lv/2) eps,
+//                         -KL partials 1/2 (1 + lv - mu^2 - e^lv)      PAeFwd (mode LATENT, 2 heads)
+//                         dz = dout W^T, dmu = dz - mu,
+//                         dlv = 1/2 dz (z - mu) + 1/2 (1 - e^lv)       PAeBwd (mode LATENT)
 //   weight gradients:     [in | 1]^T dout (ones row = bias gradient), prior -theta/s2 and
 //                         AdaGrad (infalg.py:155-161) in the epilogue   PAeWgrad
 // The first layer's A operand is gathered on the fly through idx (no copy of Xtr[idx]).
@@ -23,8 +28,9 @@ namespace vaeb {
 namespace ae {
 
 enum : int { ACT_TANH = 0, ACT_SIGMOID = 1, ACT_RELU = 2 };
-enum : int { F_ACT = 0, F_LINEAR = 1, F_OUT_BIN = 2, F_OUT_CONT = 3 };
-enum : int { B_DACT = 0, B_ZPRIOR = 1 };
+enum : int { F_ACT = 0, F_LINEAR = 1, F_OUT_BIN = 2, F_OUT_CONT = 3, F_LATENT = 4 };
+enum : int { B_DACT = 0, B_ZPRIOR = 1, B_LATENT = 2 };
+enum : int { NOISE_ZERO = 0, NOISE_HOST = 1, NOISE_PHILOX = 2 };   // eps of the F_LATENT epilogue
 constexpr float kEpsLog = 1e-7f;   // logpdf.py:86
 constexpr float kHalfLog2Pi = 0.91893853320467274178f;
 
@@ -57,6 +63,11 @@ struct PAeFwd {
     const float* Y; const int* yidx; int ldy; int y_rows;     // observations (output layer)
     float *dA, *dA2;                                          // output deltas
     float* llpart; int nct;                                   // [M][nct] log-lik partials
+    // F_LATENT (W / W2 = Wzmu / Wzlv): out = mu, out2 = lv, zout = z, llpart = -KL partials.
+    // eps: 0, eps_in[m][n] (host mode) or Philox keyed by c0 = erow[m] (the dataset row of a
+    // training step) or erow0 + m (the row's index in an evaluation call's x), c1 = n.
+    float* zout; int noise; const float* eps_in; const int* erow; uint32_t erow0;
+    uint64_t seed; int64_t step; uint32_t domain;             // c2, c3 = philox_c23(step, domain)
     rsrc_t bin, bw, bw2, by;
     DEV void prepare() {
         bin = mkbuf(in, (int64_t)in_rows * ldin * 4);
@@ -91,6 +102,25 @@ struct PAeFwd {
             const float v = acc[0][r] + bb;
             if (mode == F_ACT || mode == F_LINEAR) {
                 if (ok) out[(int64_t)m * N + n] = (mode == F_ACT) ? act_f(act, v) : v;
+                continue;
+            }
+            if (mode == F_LATENT) {
+                if constexpr (NB > 1) {
+                    const float lv = acc[1][r] + bb2;
+                    float e = 0.f;
+                    if (noise == NOISE_HOST) e = ok ? eps_in[(int64_t)m * N + n] : 0.f;
+                    else if (noise == NOISE_PHILOX)
+                        e = philox_normal(seed, m < M ? (erow ? (uint32_t)erow[m] : erow0 + (uint32_t)m) : 0u,
+                                          (uint32_t)n, philox_c23(step, domain));
+                    const float sd = fexp(0.5f * lv);
+                    if (ok) {
+                        out[(int64_t)m * N + n] = v;
+                        out2[(int64_t)m * N + n] = lv;
+                        zout[(int64_t)m * N + n] = (noise == NOISE_ZERO) ? v : v + sd * e;
+                    }
+                    const float s = sum16(ok ? 0.5f * (1.f + lv - v * v - sd * sd) : 0.f);
+                    if ((lane & 15) == 0 && m < M) llpart[(int64_t)m * nct + n0 / 16] = s;
+                }
                 continue;
             }
             if (!Y) {   // predictions only (reconstruct / decode): Xpr (+ ls2)
@@ -131,6 +161,8 @@ struct PAeFwd {
 
 // ---------------------------------------------------------------- backward (data) layer
 // din[M x N] = [dout | dout2] [W | W2]^T  (K = K1 or 2 K1), then * f'(h) or - h (Z prior).
+// B_LATENT (the decoder's first layer, N = Dz): dz = dout W^T, h / h2 / h3 = mu / lv / z,
+// din = dmu = dz - mu, din2 = dlv = 1/2 dz (z - mu) + 1/2 (1 - e^lv).
 struct PAeBwd {
     Dbg a;
     int M, N, K;
@@ -138,6 +170,7 @@ struct PAeBwd {
     const float *W, *W2;             // [N x K1] each (row n = this layer's input unit)
     const float* h; int mode, act;   // h [M x N]: activation (DACT) or Z (ZPRIOR)
     float* din;
+    const float *h2, *h3; float* din2;   // B_LATENT only
     rsrc_t bd, bd2, bw, bw2;
     DEV void prepare() {
         bd = mkbuf(dout, (int64_t)M * K1 * 4);
@@ -180,6 +213,12 @@ struct PAeBwd {
             const int m = m0 + 4 * (lane >> 4) + r;
             if (m >= M) continue;
             const float hv = h[(int64_t)m * N + n];
+            if (mode == B_LATENT) {
+                const float dz = acc[0][r], lv = h2[(int64_t)m * N + n], z = h3[(int64_t)m * N + n];
+                din[(int64_t)m * N + n] = dz - hv;
+                din2[(int64_t)m * N + n] = 0.5f * dz * (z - hv) + 0.5f * (1.f - fexp(lv));
+                continue;
+            }
             din[(int64_t)m * N + n] = (mode == B_DACT) ? acc[0][r] * dact_f(act, hv) : acc[0][r] - hv;
         }
     }
@@ -249,6 +288,26 @@ __global__ __launch_bounds__(256) void ae_loglik_kernel(const float* part, int64
         __syncthreads();
     }
     if (threadIdx.x == 0) out[slot] = (float)(sh[0] / (double)M);
+}
+
+// Gaussian latent: the step's value (loglik - KL) / M from the log-lik and the -KL partials,
+// each summed in a fixed order in fp64 -> out[slot]; sum_out (vaeb_ae_elbo): the sum itself.
+__global__ __launch_bounds__(256) void ae_elbo_kernel(const float* llpart, int64_t nll, const float* klpart, int64_t nkl,
+                                                      int M, float* out, int slot, double* sum_out) {
+    __shared__ double sh[256];
+    double s = 0.0;
+    for (int64_t i = threadIdx.x; i < nll; i += 256) s += llpart[i];
+    for (int64_t i = threadIdx.x; i < nkl; i += 256) s += klpart[i];
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        if (out) out[slot] = (float)(sh[0] / (double)M);
+        if (sum_out) *sum_out = sh[0];
+    }
 }
 
 }  // namespace ae

@@ -8,6 +8,7 @@ struct vaeb_ae {
     int64_t P = 0;
     std::vector<int64_t> oWe, obe, oWd, obd;
     int64_t oWz = 0, obz = 0, oWo = 0, obo = 0, oWl = 0, obl = 0;   // out: Wout/bout or Wmu/bmu (+ Wlogs2/blogs2)
+    int64_t oWzl = 0, obzl = 0;       // Gaussian latent: oWz / obz = Wzmu / bzmu, these = Wzlv / bzlv
     float *theta = nullptr, *acc = nullptr;
     float* data = nullptr;
     int64_t nrows = 0;
@@ -17,16 +18,61 @@ struct vaeb_ae {
     float *Z = nullptr, *dZ = nullptr, *Xpr = nullptr, *ls2 = nullptr, *dA = nullptr, *dA2 = nullptr;
     float *ll = nullptr, *outs = nullptr, *xin = nullptr;
     int outs_cap = 0;
+    // Gaussian latent (c.latent == VAEB_AE_LATENT_GAUSS): a->Z holds z
+    float *mu = nullptr, *lv = nullptr, *dmu = nullptr, *dlv = nullptr, *kl = nullptr;
+    double* esum = nullptr;           // vaeb_ae_elbo: one chunk's loglik - KL sum
+    int eps_mode = VAEB_EPS_PHILOX;
+    uint64_t seed = 0;
+    int64_t step = 0;                 // Philox step counter
+    float* eps_in = nullptr;          // pushed host eps [eps_rows x Dz]
+    int64_t eps_rows = 0, eps_cap = 0;
 };
 
 namespace {
 
 int ae_alloc(float** p, int64_t n) { return dalloc(p, (size_t)std::max<int64_t>(n, 1)); }
 
+bool ae_gauss(const vaeb_ae* a) { return a->c.latent == VAEB_AE_LATENT_GAUSS; }
+
+// eps of one latent forward (ae::PAeFwd F_LATENT): zero (the deterministic predictions),
+// rows of the pushed host eps, or Philox keyed by rows[m] / row0 + m, the step and the domain.
+struct AeNoise {
+    int mode = ae::NOISE_ZERO;
+    const float* eps = nullptr;
+    const int* rows = nullptr;
+    uint32_t row0 = 0;
+    int64_t step = 0;
+    uint32_t domain = 0;
+};
+
+// The noise of rows [r0, r0 + ...) of a call in the context's eps mode: training (domain 0,
+// keyed by the dataset rows idx) or evaluation (domain 1, stream 0, keyed by r0 + m).
+AeNoise ae_noise(const vaeb_ae* a, const int* idx, int64_t r0, int64_t step, bool eval) {
+    AeNoise z;
+    if (a->eps_mode == VAEB_EPS_HOST) {
+        z.mode = ae::NOISE_HOST;
+        z.eps = a->eps_in + r0 * a->c.Dz;
+    } else {
+        z.mode = ae::NOISE_PHILOX;
+        z.rows = idx;
+        z.row0 = (uint32_t)r0;
+        z.step = step;
+        z.domain = eval ? 1u : 0u;
+    }
+    return z;
+}
+
+int ae_host_eps_ready(const vaeb_ae* a, int64_t rows) {
+    if (a->eps_mode == VAEB_EPS_HOST && a->eps_rows != rows)
+        return fail(VAEB_ERR_STATE, "host eps mode: pushed %lld rows, the call needs %lld (call vaeb_ae_push_eps)",
+                    (long long)a->eps_rows, (long long)rows);
+    return 0;
+}
+
 // Forward through the whole network for M rows: in[ri] (ri = idx[m] when idx != null),
 // Y (observations for the loglik / deltas, nullptr for predictions), stop_at_z: encode only.
 int ae_forward(vaeb_ae* a, const float* in, int in_rows, const int* idx, int M, bool train, bool stop_at_z,
-               const float* zin) {
+               const float* zin, const AeNoise& nz = AeNoise{}) {
     const vaeb_ae_config& g = a->c;
     hipStream_t s = a->s;
     const int ne = g.n_enc, nd = g.n_dec;
@@ -45,8 +91,17 @@ int ae_forward(vaeb_ae* a, const float* in, int in_rows, const int* idx, int M, 
         p.M = M; p.N = g.Dz; p.K = a->de[ne];
         p.in = a->H[ne]; p.ldin = a->de[ne]; p.in_rows = M;
         p.W = a->theta + a->oWz; p.b = a->theta + a->obz;
-        p.mode = ae::F_LINEAR; p.out = a->Z;
-        launch_bigk<1>(s, p);
+        if (ae_gauss(a)) {
+            p.W2 = a->theta + a->oWzl; p.b2 = a->theta + a->obzl;
+            p.mode = ae::F_LATENT; p.out = a->mu; p.out2 = a->lv; p.zout = a->Z;
+            p.llpart = a->kl; p.nct = cdiv(g.Dz, 16);
+            p.noise = nz.mode; p.eps_in = nz.eps; p.erow = nz.rows; p.erow0 = nz.row0;
+            p.seed = a->seed; p.step = nz.step; p.domain = nz.domain;
+            launch_bigk<2>(s, p);
+        } else {
+            p.mode = ae::F_LINEAR; p.out = a->Z;
+            launch_bigk<1>(s, p);
+        }
         CHECK_LAUNCH();
         if (stop_at_z) return 0;
     }
@@ -99,20 +154,26 @@ int ae_bwd(vaeb_ae* a, const float* dout, const float* dout2, int K1, const floa
     p.M = M; p.N = N; p.K = dout2 ? 2 * K1 : K1;
     p.dout = dout; p.dout2 = dout2; p.K1 = K1; p.W = W; p.W2 = W2;
     p.h = h; p.mode = mode; p.act = a->c.act; p.din = din;
+    if (mode == ae::B_LATENT) { p.h = a->mu; p.h2 = a->lv; p.h3 = a->Z; p.din = a->dmu; p.din2 = a->dlv; }
     launch_bigk<1>(a->s, p);
     CHECK_LAUNCH();
     return 0;
 }
 
 // train(idx): forward + loglik, then per layer (output first) the data gradient with the
-// old weights followed by the weight update of that layer.  loglik / M -> outs[slot].
-int ae_step(vaeb_ae* a, const int* idx, int M, int slot) {
+// old weights followed by the weight update of that layer.  loglik / M -> outs[slot]
+// (Gaussian latent: (loglik - KL) / M, eps from nz; one launch more, the lv head's wgrad).
+int ae_step(vaeb_ae* a, const int* idx, int M, int slot, const AeNoise& nz = AeNoise{}) {
     const vaeb_ae_config& g = a->c;
     const int ne = g.n_enc, nd = g.n_dec, D = g.Dobs;
-    const bool cont = g.otype == VAEB_AE_CONT;
-    if (int rc = ae_forward(a, a->data, (int)a->nrows, idx, M, true, false, nullptr)) return rc;
-    hipLaunchKernelGGL(ae::ae_loglik_kernel, dim3(1), dim3(256), 0, a->s, a->ll, (int64_t)M * cdiv(D, 16), M, a->outs,
-                       slot);
+    const bool cont = g.otype == VAEB_AE_CONT, gauss = ae_gauss(a);
+    if (int rc = ae_forward(a, a->data, (int)a->nrows, idx, M, true, false, nullptr, nz)) return rc;
+    if (gauss)
+        hipLaunchKernelGGL(ae::ae_elbo_kernel, dim3(1), dim3(256), 0, a->s, a->ll, (int64_t)M * cdiv(D, 16), a->kl,
+                           (int64_t)M * cdiv(g.Dz, 16), M, a->outs, slot, (double*)nullptr);
+    else
+        hipLaunchKernelGGL(ae::ae_loglik_kernel, dim3(1), dim3(256), 0, a->s, a->ll, (int64_t)M * cdiv(D, 16), M,
+                           a->outs, slot);
     CHECK_LAUNCH();
     // output layer
     const int Hd = a->dd[nd];
@@ -126,14 +187,21 @@ int ae_step(vaeb_ae* a, const int* idx, int M, int slot) {
         const float* hin = (i == 0) ? a->Z : a->G[i];
         float* dst = (i == 0) ? a->dZ : a->dG[i];
         if (int rc = ae_bwd(a, a->dG[i + 1], nullptr, a->dd[i + 1], a->theta + a->oWd[i], nullptr, a->dd[i], M, hin,
-                            i == 0 ? ae::B_ZPRIOR : ae::B_DACT, dst)) return rc;
+                            i == 0 ? (gauss ? ae::B_LATENT : ae::B_ZPRIOR) : ae::B_DACT, dst)) return rc;
         if (int rc = ae_wgrad(a, hin, M, nullptr, a->dd[i], a->dG[i + 1], a->dd[i + 1], M, a->oWd[i], a->obd[i]))
             return rc;
     }
-    // latent layer Z = H W z + bz
-    if (int rc = ae_bwd(a, a->dZ, nullptr, g.Dz, a->theta + a->oWz, nullptr, a->de[ne], M, a->H[ne], ae::B_DACT,
-                        a->dH[ne])) return rc;
-    if (int rc = ae_wgrad(a, a->H[ne], M, nullptr, a->de[ne], a->dZ, g.Dz, M, a->oWz, a->obz)) return rc;
+    // latent layer Z = H W z + bz, or the two heads [mu | lv] = H [Wzmu | Wzlv] + [bzmu | bzlv]
+    if (gauss) {
+        if (int rc = ae_bwd(a, a->dmu, a->dlv, g.Dz, a->theta + a->oWz, a->theta + a->oWzl, a->de[ne], M, a->H[ne],
+                            ae::B_DACT, a->dH[ne])) return rc;
+        if (int rc = ae_wgrad(a, a->H[ne], M, nullptr, a->de[ne], a->dmu, g.Dz, M, a->oWz, a->obz)) return rc;
+        if (int rc = ae_wgrad(a, a->H[ne], M, nullptr, a->de[ne], a->dlv, g.Dz, M, a->oWzl, a->obzl)) return rc;
+    } else {
+        if (int rc = ae_bwd(a, a->dZ, nullptr, g.Dz, a->theta + a->oWz, nullptr, a->de[ne], M, a->H[ne], ae::B_DACT,
+                            a->dH[ne])) return rc;
+        if (int rc = ae_wgrad(a, a->H[ne], M, nullptr, a->de[ne], a->dZ, g.Dz, M, a->oWz, a->obz)) return rc;
+    }
     // encoder layers (top down); no data gradient into X
     for (int i = ne - 1; i >= 0; --i) {
         if (i > 0)
@@ -213,6 +281,8 @@ int vaeb_ae_create(const vaeb_ae_config* cfg, vaeb_ae** out) {
     for (int i = 0; i < g.n_dec; ++i) if (g.Ddec[i] <= 0) return fail(VAEB_ERR_ARG, "Ddec[%d] <= 0", i);
     if (g.otype != VAEB_AE_BINARY && g.otype != VAEB_AE_CONT) return fail(VAEB_ERR_ARG, "otype must be binary|cont");
     if (g.act < 0 || g.act > 2) return fail(VAEB_ERR_ARG, "bad activation");
+    if (g.latent != VAEB_AE_LATENT_POINT && g.latent != VAEB_AE_LATENT_GAUSS)
+        return fail(VAEB_ERR_ARG, "latent must be VAEB_AE_LATENT_POINT | VAEB_AE_LATENT_GAUSS (got %d)", g.latent);
     if (!(g.s2 > 0.f) || !(g.eta > 0.f)) return fail(VAEB_ERR_ARG, "s2 and eta must be > 0");
     auto* a = new vaeb_ae();
     a->c = g;
@@ -228,8 +298,16 @@ int vaeb_ae_create(const vaeb_ae_config* cfg, vaeb_ae** out) {
     int64_t o = 0;
     for (int i = 0; i < g.n_enc; ++i) { a->oWe.push_back(o); o += (int64_t)a->de[i] * a->de[i + 1]; }
     for (int i = 0; i < g.n_enc; ++i) { a->obe.push_back(o); o += a->de[i + 1]; }
-    a->oWz = o; o += (int64_t)a->de[g.n_enc] * g.Dz;
-    a->obz = o; o += g.Dz;
+    const int64_t HZ = (int64_t)a->de[g.n_enc] * g.Dz;
+    if (g.latent == VAEB_AE_LATENT_GAUSS) {   // as the cont output: Wzmu, Wzlv, bzmu, bzlv
+        a->oWz = o; o += HZ;
+        a->oWzl = o; o += HZ;
+        a->obz = o; o += g.Dz;
+        a->obzl = o; o += g.Dz;
+    } else {
+        a->oWz = o; o += HZ;
+        a->obz = o; o += g.Dz;
+    }
     for (int i = 0; i < g.n_dec; ++i) { a->oWd.push_back(o); o += (int64_t)a->dd[i] * a->dd[i + 1]; }
     for (int i = 0; i < g.n_dec; ++i) { a->obd.push_back(o); o += a->dd[i + 1]; }
     const int64_t HD = (int64_t)a->dd[g.n_dec] * g.Dobs;
@@ -267,6 +345,14 @@ int vaeb_ae_create(const vaeb_ae_config* cfg, vaeb_ae** out) {
     rc = rc ? rc : ae_alloc(&a->dA2, B * g.Dobs);
     rc = rc ? rc : ae_alloc(&a->ll, B * cdiv(g.Dobs, 16));
     rc = rc ? rc : ae_alloc(&a->xin, B * std::max(g.Dobs, g.Dz));
+    if (ae_gauss(a)) {
+        rc = rc ? rc : ae_alloc(&a->mu, B * g.Dz);
+        rc = rc ? rc : ae_alloc(&a->lv, B * g.Dz);
+        rc = rc ? rc : ae_alloc(&a->dmu, B * g.Dz);
+        rc = rc ? rc : ae_alloc(&a->dlv, B * g.Dz);
+        rc = rc ? rc : ae_alloc(&a->kl, B * cdiv(g.Dz, 16));
+        rc = rc ? rc : dalloc(&a->esum, 1);
+    }
     rc = rc ? rc : ae_reserve(a, (int)B, 1);
     if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(VAEB_ERR_HIP, "device init failed");
     if (rc) { vaeb_ae_destroy(a); return rc; }
@@ -278,10 +364,11 @@ int vaeb_ae_destroy(vaeb_ae* a) {
     if (!a) return 0;
     if (a->s) hipStreamSynchronize(a->s);
     std::vector<float*> ps = {a->theta, a->acc, a->data, a->Z, a->dZ, a->Xpr, a->ls2, a->dA, a->dA2, a->ll, a->outs,
-                              a->xin};
+                              a->xin, a->mu, a->lv, a->dmu, a->dlv, a->kl, a->eps_in};
     for (auto* v : {&a->H, &a->G, &a->dH, &a->dG}) ps.insert(ps.end(), v->begin(), v->end());
     for (float* p : ps) if (p) hipFree(p);
     if (a->idx) hipFree(a->idx);
+    if (a->esum) hipFree(a->esum);
     if (a->s) hipStreamDestroy(a->s);
     delete a;
     return 0;
@@ -312,12 +399,18 @@ int vaeb_ae_train_many(vaeb_ae* a, const int32_t* idx, int32_t n, int32_t batch,
     if (!a || !idx || !out || n <= 0 || batch <= 0) return fail(VAEB_ERR_ARG, "bad arguments");
     if (batch > a->c.max_batch) return fail(VAEB_ERR_ARG, "batch %d > max_batch %d", batch, a->c.max_batch);
     if (int rc = ae_check_idx(a, idx, n)) return rc;
+    const bool gauss = ae_gauss(a);
+    if (gauss)
+        if (int rc = ae_host_eps_ready(a, n)) return rc;
     const int nb = cdiv(n, batch);
     if (int rc = ae_reserve(a, n, nb)) return rc;
     HIP_TRY(hipMemcpyAsync(a->idx, idx, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, a->s));
     for (int j = 0; j < nb; ++j) {
         const int lb = j * batch, m = std::min(batch, n - lb);
-        if (int rc = ae_step(a, a->idx + lb, m, j)) return rc;
+        if (gauss) {   // each step draws at the counter, then advances it
+            if (int rc = ae_step(a, a->idx + lb, m, j, ae_noise(a, a->idx + lb, lb, a->step, false))) return rc;
+            ++a->step;
+        } else if (int rc = ae_step(a, a->idx + lb, m, j)) return rc;
     }
     HIP_TRY(hipMemcpyAsync(out, a->outs, sizeof(float) * (size_t)nb, hipMemcpyDeviceToHost, a->s));
     HIP_TRY(hipStreamSynchronize(a->s));
@@ -332,5 +425,97 @@ int vaeb_ae_train(vaeb_ae* a, const int32_t* idx, int32_t n, float* out) {
 int vaeb_ae_reconstruct(vaeb_ae* a, const float* x, int64_t n, float* out) { return ae_predict(a, x, n, out, 0); }
 int vaeb_ae_encode(vaeb_ae* a, const float* x, int64_t n, float* z) { return ae_predict(a, x, n, z, 1); }
 int vaeb_ae_decode(vaeb_ae* a, const float* z, int64_t n, float* out) { return ae_predict(a, z, n, out, 2); }
+
+// ------------------------------------------------------------------ Gaussian latent
+#define AE_NEED_GAUSS(a, fn)                                                                            \
+    do {                                                                                                \
+        if (!(a)) return fail(VAEB_ERR_ARG, "null argument");                                           \
+        if (!ae_gauss(a)) return fail(VAEB_ERR_ARG, fn " needs a VAEB_AE_LATENT_GAUSS context");        \
+    } while (0)
+
+int vaeb_ae_set_eps_mode(vaeb_ae* a, int32_t mode, uint64_t seed) {
+    AE_NEED_GAUSS(a, "vaeb_ae_set_eps_mode");
+    if (mode != VAEB_EPS_PHILOX && mode != VAEB_EPS_HOST) return fail(VAEB_ERR_ARG, "bad eps mode");
+    HIP_TRY(hipStreamSynchronize(a->s));
+    a->eps_mode = mode;
+    a->seed = seed;
+    return 0;
+}
+
+int vaeb_ae_push_eps(vaeb_ae* a, const float* eps, int64_t rows) {
+    AE_NEED_GAUSS(a, "vaeb_ae_push_eps");
+    if (!eps || rows <= 0) return fail(VAEB_ERR_ARG, "bad eps arguments");
+    const int64_t n = rows * a->c.Dz;
+    HIP_TRY(hipStreamSynchronize(a->s));
+    if (n > a->eps_cap) {
+        if (a->eps_in) hipFree(a->eps_in);
+        a->eps_in = nullptr;
+        a->eps_cap = a->eps_rows = 0;
+        if (int rc = dalloc(&a->eps_in, (size_t)n)) return rc;
+        a->eps_cap = n;
+    }
+    HIP_TRY(hipMemcpy(a->eps_in, eps, sizeof(float) * (size_t)n, hipMemcpyHostToDevice));
+    a->eps_rows = rows;
+    return 0;
+}
+
+int vaeb_ae_set_step(vaeb_ae* a, int64_t step) {
+    AE_NEED_GAUSS(a, "vaeb_ae_set_step");
+    a->step = step;
+    return 0;
+}
+
+int vaeb_ae_get_step(vaeb_ae* a, int64_t* step) {
+    AE_NEED_GAUSS(a, "vaeb_ae_get_step");
+    if (!step) return fail(VAEB_ERR_ARG, "null argument");
+    *step = a->step;
+    return 0;
+}
+
+int vaeb_ae_encode_dist(vaeb_ae* a, const float* x, int64_t n, float* out_mu, float* out_lv, float* out_z) {
+    AE_NEED_GAUSS(a, "vaeb_ae_encode_dist");
+    if (!x || n <= 0) return fail(VAEB_ERR_ARG, "bad arguments");
+    const vaeb_ae_config& g = a->c;
+    if (out_z)
+        if (int rc = ae_host_eps_ready(a, n)) return rc;
+    for (int64_t r0 = 0; r0 < n; r0 += g.max_batch) {
+        const int rows = (int)std::min<int64_t>(g.max_batch, n - r0);
+        HIP_TRY(hipMemcpyAsync(a->xin, x + r0 * g.Dobs, sizeof(float) * (size_t)rows * g.Dobs, hipMemcpyHostToDevice,
+                               a->s));
+        const AeNoise nz = out_z ? ae_noise(a, nullptr, r0, a->step, true) : AeNoise{};
+        if (int rc = ae_forward(a, a->xin, rows, nullptr, rows, false, true, nullptr, nz)) return rc;
+        const size_t nb = sizeof(float) * (size_t)rows * g.Dz;
+        if (out_mu) HIP_TRY(hipMemcpyAsync(out_mu + r0 * g.Dz, a->mu, nb, hipMemcpyDeviceToHost, a->s));
+        if (out_lv) HIP_TRY(hipMemcpyAsync(out_lv + r0 * g.Dz, a->lv, nb, hipMemcpyDeviceToHost, a->s));
+        if (out_z) HIP_TRY(hipMemcpyAsync(out_z + r0 * g.Dz, a->Z, nb, hipMemcpyDeviceToHost, a->s));
+        HIP_TRY(hipStreamSynchronize(a->s));
+    }
+    return 0;
+}
+
+int vaeb_ae_elbo(vaeb_ae* a, const float* x, int64_t n, double* out_sum) {
+    AE_NEED_GAUSS(a, "vaeb_ae_elbo");
+    if (!x || !out_sum || n <= 0) return fail(VAEB_ERR_ARG, "bad arguments");
+    const vaeb_ae_config& g = a->c;
+    if (int rc = ae_host_eps_ready(a, n)) return rc;
+    double total = 0.0;
+    for (int64_t r0 = 0; r0 < n; r0 += g.max_batch) {
+        const int rows = (int)std::min<int64_t>(g.max_batch, n - r0);
+        HIP_TRY(hipMemcpyAsync(a->xin, x + r0 * g.Dobs, sizeof(float) * (size_t)rows * g.Dobs, hipMemcpyHostToDevice,
+                               a->s));
+        if (int rc = ae_forward(a, a->xin, rows, nullptr, rows, true, false, nullptr,
+                                ae_noise(a, nullptr, r0, a->step, true))) return rc;
+        hipLaunchKernelGGL(ae::ae_elbo_kernel, dim3(1), dim3(256), 0, a->s, a->ll, (int64_t)rows * cdiv(g.Dobs, 16),
+                           a->kl, (int64_t)rows * cdiv(g.Dz, 16), rows, (float*)nullptr, 0, a->esum);
+        CHECK_LAUNCH();
+        double part = 0.0;
+        HIP_TRY(hipMemcpyAsync(&part, a->esum, sizeof(double), hipMemcpyDeviceToHost, a->s));
+        HIP_TRY(hipStreamSynchronize(a->s));
+        total += part;
+    }
+    *out_sum = total;
+    return 0;
+}
+#undef AE_NEED_GAUSS
 
 }  // extern "C"
