@@ -300,6 +300,23 @@ int vaeb_ae_encode_dist(vaeb_ae* ae, const float* x, int64_t n, float* out_mu, f
 /* Forward-only sum of loglik + negKL over n rows of host x with evaluation noise, in max_batch
  * chunks (no theta prior).  Changes no parameter, accumulator or step. */
 int vaeb_ae_elbo(vaeb_ae* ae, const float* x, int64_t n, double* out_sum);
+/* The K-sample importance-weighted estimate of sum_i log p(x_i) for host x [n x Dobs], with the
+ * encoder as the proposal (vaeb_marginal_ll's quantity on the layer stack).  Per row, mu and lv
+ * are computed once, then for k = 0..K-1
+ *   z_k = mu + exp(lv / 2) eps_k,  log w_k = loglik_row(x | z_k) + 1/2 sum_j (eps_kj^2 + lv_j - z_kj^2),
+ *   IW_K(x) = logsumexp_k log w_k - log K,
+ * loglik_row being the output layer above (binary: the 1e-7 inside the logs); no theta prior and
+ * no analytic KL enter.  out_sum: the sum of the row values (double, fixed order).  out_rows:
+ * IW_K per row [n], or NULL.  1 <= K <= 2^20, else VAEB_ERR_ARG before the device is touched.
+ * Noise.  PHILOX: sample k draws from evaluation stream k + 1 (domain 1 | (k + 1) << 1): c0 = the
+ * row's index in the x passed to the call, c1 = j, c2, c3 from the current step, which stays.
+ * HOST: the pushed eps must hold exactly n * K rows, sample k of row i at row k * n + i
+ * (VAEB_ERR_STATE otherwise), and stays.
+ * A non-finite log w_k makes that row's value and *out_sum NaN (never dropped); other rows are
+ * unaffected.  A row's value does not depend on max_batch.  Changes no parameter, accumulator,
+ * step or pushed eps.  Device memory does not grow with K or n (scratch sized by max_batch,
+ * allocated on the first call). */
+int vaeb_ae_marginal_ll(vaeb_ae* ae, const float* x, int64_t n, int32_t K, double* out_sum, float* out_rows);
 
 #ifdef __cplusplus
 }

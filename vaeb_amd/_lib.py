@@ -38,7 +38,7 @@ EXPORTS = [
     "vaeb_ae_get_params", "vaeb_ae_set_adagrad_state", "vaeb_ae_get_adagrad_state", "vaeb_ae_train",
     "vaeb_ae_train_many", "vaeb_ae_reconstruct", "vaeb_ae_encode", "vaeb_ae_decode",
     "vaeb_ae_set_eps_mode", "vaeb_ae_push_eps", "vaeb_ae_set_step", "vaeb_ae_get_step", "vaeb_ae_encode_dist",
-    "vaeb_ae_elbo",
+    "vaeb_ae_elbo", "vaeb_ae_marginal_ll",
 ]
 DIAG_EXPORTS = ["vaeb_profile_steps", "vaeb_kernel_name", "vaeb_debug_timeline", "vaeb_test_gemm_bf16",
                 "vaeb_bench_gemm_bf16", "vaeb_graph_status", "vaeb_comm_info", "vaeb_time_update_many", "vaeb_busy",
@@ -174,6 +174,7 @@ def load():
         "vaeb_ae_get_step": ([_P, ctypes.POINTER(_I64)], ctypes.c_int),
         "vaeb_ae_encode_dist": ([_P, _F, _I64, _F, _F, _F], ctypes.c_int),
         "vaeb_ae_elbo": ([_P, _F, _I64, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
+        "vaeb_ae_marginal_ll": ([_P, _F, _I64, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), _F], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -669,3 +670,13 @@ class AEContext:
         out = ctypes.c_double()
         check(self.lib.vaeb_ae_elbo(self.h, fptr(x), x.shape[0], ctypes.byref(out)))
         return out.value
+
+    def marginal_ll(self, x, K, rows=False):
+        """K-sample importance-weighted estimate of sum_i log p(x_i) (vaeb_ae_marginal_ll); with
+        rows=True also the per-row values: (sum, [n])."""
+        x = np.ascontiguousarray(x, np.float32)
+        out = ctypes.c_double()
+        r = np.empty(x.shape[0], np.float32) if rows else None
+        check(self.lib.vaeb_ae_marginal_ll(self.h, fptr(x), x.shape[0], int(K), ctypes.byref(out),
+                                           fptr(r) if rows else None))
+        return (out.value, r) if rows else out.value

@@ -135,7 +135,11 @@ def ConstructVAE(Xtr, Denc=(500,), Dz=20, Ddec=(500,), f="tanh", s2=1.0, inf=Non
     [..., Wzmu, Wzlv, bzmu, bzlv, ...].  train(idx) takes one AdaGrad step on the ELBO of the
     rows Xtr[idx] (one Philox draw per row and latent, keyed by `seed`, the dataset row and the
     step) and returns (loglik - KL) / len(idx); encode(X) is mu, reconstruct(X) decodes z = mu.
-    train.ctx is the engine context; train.elbo(X) the forward-only sum of loglik - KL."""
+    train.ctx is the engine context; train.elbo(X) the forward-only sum of loglik - KL;
+    train.marginal_ll(X, K, rows=False) the K-sample importance-weighted estimate of
+    sum_i log p(x_i) with the encoder as the proposal (forward only; rows=True: (sum, per-row
+    values) -- the figure that ranks a deep model against the one-hidden-layer VAEB's
+    marginal_likelihood)."""
     ctx, theta = _construct("gauss", Xtr, Denc, Dz, Ddec, f, s2, inf, otype, max_batch, device)
     ctx.set_eps_mode(_lib.EPS_PHILOX, seed)
 
@@ -144,6 +148,7 @@ def ConstructVAE(Xtr, Denc=(500,), Dz=20, Ddec=(500,), f="tanh", s2=1.0, inf=Non
 
     train.ctx = ctx
     train.elbo = lambda X: ctx.elbo(_values(X))
+    train.marginal_ll = lambda X, K, rows=False: ctx.marginal_ll(_values(X), K, rows=rows)
     return train, ctx.reconstruct, ctx.encode, ctx.decode, theta
 
 

@@ -61,7 +61,8 @@ struct PAeFwd {
     int mode, act;
     float *out, *out2;                                        // activations / Xpr (+ ls2)
     const float* Y; const int* yidx; int ldy; int y_rows;     // observations (output layer)
-    float *dA, *dA2;                                          // output deltas
+    float *dA, *dA2;                                          // output deltas; Y with dA == nullptr: value
+                                                              // only (llpart; no out / out2 / delta stores)
     float* llpart; int nct;                                   // [M][nct] log-lik partials
     // F_LATENT (W / W2 = Wzmu / Wzlv): out = mu, out2 = lv, zout = z, llpart = -KL partials.
     // eps: 0, eps_in[m][n] (host mode) or Philox keyed by c0 = erow[m] (the dataset row of a
@@ -135,10 +136,12 @@ struct PAeFwd {
             if (mode == F_OUT_BIN) {
                 const float P = sigmoidf(v);
                 ll = y * flog(P + kEpsLog) + (1.f - y) * flog(1.f - P + kEpsLog);
-                const float dP = y / (P + kEpsLog) - (1.f - y) / (1.f - P + kEpsLog);
-                if (ok) {
-                    out[(int64_t)m * N + n] = P;
-                    dA[(int64_t)m * N + n] = dP * P * (1.f - P);
+                if (dA) {
+                    const float dP = y / (P + kEpsLog) - (1.f - y) / (1.f - P + kEpsLog);
+                    if (ok) {
+                        out[(int64_t)m * N + n] = P;
+                        dA[(int64_t)m * N + n] = dP * P * (1.f - P);
+                    }
                 }
             } else {
                 float ls2 = bb2;
@@ -146,7 +149,7 @@ struct PAeFwd {
                 const float mu = sigmoidf(v);
                 const float rr = y - mu, e = fexp(-ls2);
                 ll = -kHalfLog2Pi - 0.5f * ls2 - 0.5f * rr * rr * e;
-                if (ok) {
+                if (ok && dA) {
                     out[(int64_t)m * N + n] = mu;
                     out2[(int64_t)m * N + n] = ls2;
                     dA[(int64_t)m * N + n] = rr * e * mu * (1.f - mu);

@@ -20,7 +20,11 @@ struct vaeb_ae {
     int outs_cap = 0;
     // Gaussian latent (c.latent == VAEB_AE_LATENT_GAUSS): a->Z holds z
     float *mu = nullptr, *lv = nullptr, *dmu = nullptr, *dlv = nullptr, *kl = nullptr;
-    double* esum = nullptr;           // vaeb_ae_elbo: one chunk's loglik - KL sum
+    double* esum = nullptr;           // vaeb_ae_elbo / vaeb_ae_marginal_ll: one chunk's sum
+    // vaeb_ae_marginal_ll scratch (allocated on first use): latent terms [max_batch], running
+    // (max, sum) [2 max_batch], row values [max_batch]; the observation row of each stacked row
+    float* iw = nullptr;
+    int* iw_yrow = nullptr;
     int eps_mode = VAEB_EPS_PHILOX;
     uint64_t seed = 0;
     int64_t step = 0;                 // Philox step counter
@@ -71,8 +75,9 @@ int ae_host_eps_ready(const vaeb_ae* a, int64_t rows) {
 
 // Forward through the whole network for M rows: in[ri] (ri = idx[m] when idx != null),
 // Y (observations for the loglik / deltas, nullptr for predictions), stop_at_z: encode only.
+// value_only (with train and zin): the output layer leaves the loglik partials and nothing else.
 int ae_forward(vaeb_ae* a, const float* in, int in_rows, const int* idx, int M, bool train, bool stop_at_z,
-               const float* zin, const AeNoise& nz = AeNoise{}) {
+               const float* zin, const AeNoise& nz = AeNoise{}, bool value_only = false) {
     const vaeb_ae_config& g = a->c;
     hipStream_t s = a->s;
     const int ne = g.n_enc, nd = g.n_dec;
@@ -120,13 +125,14 @@ int ae_forward(vaeb_ae* a, const float* in, int in_rows, const int* idx, int M, 
     p.W = a->theta + a->oWo; p.b = a->theta + a->obo;
     p.out = a->Xpr;
     if (train) { p.Y = in; p.yidx = idx; p.ldy = g.Dobs; p.y_rows = in_rows; }
-    p.dA = a->dA; p.llpart = a->ll; p.nct = cdiv(g.Dobs, 16);
+    p.dA = value_only ? nullptr : a->dA; p.llpart = a->ll; p.nct = cdiv(g.Dobs, 16);
     if (g.otype == VAEB_AE_BINARY) {
         p.mode = ae::F_OUT_BIN;
         launch_bigk<1>(s, p);
     } else {
         p.mode = ae::F_OUT_CONT;
-        p.W2 = a->theta + a->oWl; p.b2 = a->theta + a->obl; p.out2 = a->ls2; p.dA2 = a->dA2;
+        p.W2 = a->theta + a->oWl; p.b2 = a->theta + a->obl; p.out2 = a->ls2;
+        p.dA2 = value_only ? nullptr : a->dA2;
         launch_bigk<2>(s, p);
     }
     CHECK_LAUNCH();
@@ -364,10 +370,11 @@ int vaeb_ae_destroy(vaeb_ae* a) {
     if (!a) return 0;
     if (a->s) hipStreamSynchronize(a->s);
     std::vector<float*> ps = {a->theta, a->acc, a->data, a->Z, a->dZ, a->Xpr, a->ls2, a->dA, a->dA2, a->ll, a->outs,
-                              a->xin, a->mu, a->lv, a->dmu, a->dlv, a->kl, a->eps_in};
+                              a->xin, a->mu, a->lv, a->dmu, a->dlv, a->kl, a->eps_in, a->iw};
     for (auto* v : {&a->H, &a->G, &a->dH, &a->dG}) ps.insert(ps.end(), v->begin(), v->end());
     for (float* p : ps) if (p) hipFree(p);
     if (a->idx) hipFree(a->idx);
+    if (a->iw_yrow) hipFree(a->iw_yrow);
     if (a->esum) hipFree(a->esum);
     if (a->s) hipStreamDestroy(a->s);
     delete a;
@@ -510,6 +517,57 @@ int vaeb_ae_elbo(vaeb_ae* a, const float* x, int64_t n, double* out_sum) {
         CHECK_LAUNCH();
         double part = 0.0;
         HIP_TRY(hipMemcpyAsync(&part, a->esum, sizeof(double), hipMemcpyDeviceToHost, a->s));
+        HIP_TRY(hipStreamSynchronize(a->s));
+        total += part;
+    }
+    *out_sum = total;
+    return 0;
+}
+
+int vaeb_ae_marginal_ll(vaeb_ae* a, const float* x, int64_t n, int32_t K, double* out_sum, float* out_rows) {
+    AE_NEED_GAUSS(a, "vaeb_ae_marginal_ll");
+    if (!x || !out_sum || n <= 0) return fail(VAEB_ERR_ARG, "bad arguments");
+    if (K < 1 || K > (1 << 20))
+        return fail(VAEB_ERR_ARG, "K = %d: 1 to 2^20 samples (the Philox sample-stream field)", K);
+    if (int rc = ae_host_eps_ready(a, n * K)) return rc;
+    const vaeb_ae_config& g = a->c;
+    const int B = g.max_batch, nct = cdiv(g.Dobs, 16);
+    if (!a->iw)
+        if (int rc = ae_alloc(&a->iw, 4 * (int64_t)B)) return rc;
+    if (!a->iw_yrow)
+        if (int rc = dalloc(&a->iw_yrow, (size_t)B)) return rc;
+    IwArgs w{};
+    w.nctD = nct; w.K = K; w.logK = (float)std::log((double)K);
+    w.lat = a->iw; w.ms = a->iw + B; w.rows = a->iw + 3 * (int64_t)B; w.lp_part = a->ll;
+    ae::AeIwArgs q{};
+    q.Dz = g.Dz; q.n = n;
+    q.eps_mode = a->eps_mode == VAEB_EPS_HOST ? 1 : 0;
+    q.seed = a->seed; q.step = a->step; q.eps_in = a->eps_in;
+    q.mu = a->mu; q.lv = a->lv; q.z = a->Z; q.lat = a->iw; q.yrow = a->iw_yrow;
+    double total = 0.0;
+    for (int64_t r0 = 0; r0 < n; r0 += B) {
+        const int R = (int)std::min<int64_t>(B, n - r0);
+        HIP_TRY(hipMemcpyAsync(a->xin, x + r0 * g.Dobs, sizeof(float) * (size_t)R * g.Dobs, hipMemcpyHostToDevice, a->s));
+        if (int rc = ae_forward(a, a->xin, R, nullptr, R, false, true, nullptr)) return rc;   // mu, lv: once
+        const int smax = std::max(1, B / R);   // sample planes per pass: S * R <= max_batch stacked rows
+        w.Mb = w.Mbp = q.R = R;
+        q.row0 = r0;
+        for (int k0 = 0; k0 < K; k0 += smax) {
+            const int S = std::min(smax, K - k0);
+            w.k0 = q.k0 = k0; w.S = q.S = S;
+            hipLaunchKernelGGL(ae::ae_iw_sample_kernel, dim3(cdiv(S * R, 16)), dim3(256), 0, a->s, q);
+            CHECK_LAUNCH();
+            if (int rc = ae_forward(a, a->xin, R, a->iw_yrow, S * R, true, false, a->Z, AeNoise{}, true)) return rc;
+            hipLaunchKernelGGL(iw_lse_kernel, dim3(cdiv(R, 256)), dim3(256), 0, a->s, w);
+            CHECK_LAUNCH();
+        }
+        HIP_TRY(hipMemsetAsync(a->esum, 0, sizeof(double), a->s));
+        hipLaunchKernelGGL(iw_sum_kernel, dim3(1), dim3(256), 0, a->s, w.rows, (int64_t)R, a->esum);
+        CHECK_LAUNCH();
+        double part = 0.0;
+        HIP_TRY(hipMemcpyAsync(&part, a->esum, sizeof(double), hipMemcpyDeviceToHost, a->s));
+        if (out_rows)
+            HIP_TRY(hipMemcpyAsync(out_rows + r0, w.rows, sizeof(float) * (size_t)R, hipMemcpyDeviceToHost, a->s));
         HIP_TRY(hipStreamSynchronize(a->s));
         total += part;
     }

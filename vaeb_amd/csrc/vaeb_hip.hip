@@ -27,6 +27,7 @@
 #include "iwae.hpp"
 #include "h16_engines.hpp"
 #include "ae_mlp.hpp"
+#include "ae_iwae.hpp"
 
 using namespace vaeb;
 
