@@ -236,7 +236,20 @@ enum vaeb_act      { VAEB_ACT_TANH = 0, VAEB_ACT_SIGMOID = 1, VAEB_ACT_RELU = 2 
  *   negKL = 1/2 sum_{m,j} (1 + lv - mu^2 - exp(lv))     (replaces the N(0, 1) prior on Z),
  *   f = loglik + negKL + N(0, s2) prior on theta        (maximised by the same AdaGrad),
  * and train(idx) returns (loglik + negKL) / M.  In theta, [Wz, bz] become
- * [Wzmu, Wzlv, bzmu, bzlv] (the cont output's convention); everything else keeps its place. */
+ * [Wzmu, Wzlv, bzmu, bzlv] (the cont output's convention); everything else keeps its place.
+ *
+ * iw_samples = K >= 2 (GAUSS only; K on a POINT context, K < 0 or K > 2^20 is VAEB_ERR_ARG at
+ * create; 0 and 1 are the ELBO step above, on its own code path): train on the K-sample
+ * importance-weighted bound (Burda et al. 2016).  mu and lv once per row, then for k = 0..K-1
+ *   z_k = mu + exp(lv / 2) eps_k,  log w_k = loglik_row(x | z_k) + 1/2 sum_j (eps_kj^2 + lv_j - z_kj^2)
+ *   L_K = sum_m [logsumexp_k log w_mk - log K]           (vaeb_ae_marginal_ll's quantity)
+ *   f   = L_K + N(0, s2) prior on theta,  train(idx) returns L_K / M,
+ * with the reparameterised gradient sum_m sum_k wn_mk grad log w_mk - theta / s2,
+ * wn_mk = w_mk / sum_k' w_mk' (no analytic KL enters).  The K sample planes are stacked in the
+ * context's activation buffers, so a step needs K * M <= max_batch: otherwise VAEB_ERR_ARG before
+ * the device is touched, with theta, the accumulators and the step unchanged.  A non-finite
+ * log w_mk makes the step's value NaN (never dropped).  The evaluation calls behave exactly as on
+ * an ELBO context. */
 enum vaeb_ae_latent { VAEB_AE_LATENT_POINT = 0, VAEB_AE_LATENT_GAUSS = 1 };
 
 typedef struct vaeb_ae_config {
@@ -253,7 +266,8 @@ typedef struct vaeb_ae_config {
     int32_t max_batch;                    /* largest idx list / predict chunk                */
     int32_t device;
     int32_t latent;                       /* enum vaeb_ae_latent (0: the point latent)       */
-    int32_t reserved[3];
+    int32_t iw_samples;                   /* K of the training objective (below); 0, 1: ELBO */
+    int32_t reserved[2];
 } vaeb_ae_config;
 
 typedef struct vaeb_ae vaeb_ae;
@@ -288,7 +302,12 @@ int vaeb_ae_decode(vaeb_ae* ae, const float* z, int64_t n, float* out);        /
  *               the call; c2, c3 = step ^ 1 << 63 (stream 0), at the current step, which stays.
  * HOST: the caller pushes eps [rows x Dz] in the row order of the next call (vaeb_ae_train_many:
  * of the whole idx list); a call that draws noise for another row count is VAEB_ERR_STATE.  The
- * pushed eps stays until the next push. */
+ * pushed eps stays until the next push.
+ * Training with iw_samples = K >= 2.  PHILOX: sample k of dataset row idx[m] is the draw at
+ * c0 = idx[m], c1 = j, c2, c3 = the step with sample stream k (domain k << 1: the training domain),
+ * so sample 0 is the ELBO context's draw for the same seed, row and step; each step advances the
+ * step counter by one.  HOST: the push holds exactly K * n rows, n the length of the whole idx
+ * list of the call, sample k of list position i at row k * n + i (VAEB_ERR_STATE otherwise). */
 int vaeb_ae_set_eps_mode(vaeb_ae* ae, int32_t mode, uint64_t seed);
 int vaeb_ae_push_eps(vaeb_ae* ae, const float* eps, int64_t rows);
 int vaeb_ae_set_step(vaeb_ae* ae, int64_t step);    /* Philox step counter */

@@ -67,7 +67,7 @@ class AEConfigC(ctypes.Structure):
         ("Dz", ctypes.c_int32), ("n_dec", ctypes.c_int32), ("Ddec", ctypes.c_int32 * 8),
         ("otype", ctypes.c_int32), ("act", ctypes.c_int32), ("s2", ctypes.c_float), ("eta", ctypes.c_float),
         ("max_batch", ctypes.c_int32), ("device", ctypes.c_int32), ("latent", ctypes.c_int32),
-        ("reserved", ctypes.c_int32 * 3),
+        ("iw_samples", ctypes.c_int32), ("reserved", ctypes.c_int32 * 2),
     ]
 
 
@@ -545,10 +545,11 @@ class Context:
 
 class AEContext:
     """One degenerate-vae autoencoder (vaeb_ae_*) on one GPU; latent="gauss": the deep VAE on
-    the same layer stack (include/vaeb_hip.h enum vaeb_ae_latent)."""
+    the same layer stack (include/vaeb_hip.h enum vaeb_ae_latent); iw_samples = K >= 2: train on
+    the K-sample importance-weighted bound (K * len(idx) <= max_batch per step)."""
 
     def __init__(self, Dobs, Denc, Dz, Ddec, otype="binary", act="tanh", s2=1.0, eta=0.01, max_batch=100,
-                 device=0, latent="point"):
+                 device=0, latent="point", iw_samples=1):
         self.lib = load()
         c = AEConfigC()
         c.Dobs, c.Dz = int(Dobs), int(Dz)
@@ -567,6 +568,8 @@ class AEContext:
         if latent not in AE_LATENT:
             raise VaebError(f"latent {latent!r} not supported (point | gauss)")
         c.latent = AE_LATENT[latent]
+        c.iw_samples = int(iw_samples)
+        self.iw_samples = c.iw_samples
         self.cfg = c
         self.Dobs, self.Dz = c.Dobs, c.Dz
         self.h = _P()

@@ -92,7 +92,7 @@ class _AccArena:
         self.ctx.set_adagrad_state(flat)
 
 
-def _construct(latent, Xtr, Denc, Dz, Ddec, f, s2, inf, otype, max_batch, device):
+def _construct(latent, Xtr, Denc, Dz, Ddec, f, s2, inf, otype, max_batch, device, iw_samples=1):
     """The shared body of ConstructAE / ConstructVAE; returns (ctx, theta)."""
     if otype not in ("binary", "cont"):
         raise ValueError("otype currently only supports binary.")   # ae.py:74-75 (and cont)
@@ -103,9 +103,10 @@ def _construct(latent, Xtr, Denc, Dz, Ddec, f, s2, inf, otype, max_batch, device
     shapes = param_shapes(Dobs, Denc, Dz, Ddec, otype, latent)
     # mlp.WeightMatrix / BiasVector: N(0, 0.01) from the global RNG, construction order
     theta0 = [np.random.normal(0.0, 0.01, size=s).astype(np.float32) for _, s in shapes]
-    mb = int(max_batch) if max_batch else max(100, min(4096, Xtr.shape[0]))
+    K = max(1, int(iw_samples))   # the K sample planes of a step are stacked inside max_batch
+    mb = int(max_batch) if max_batch else max(100 * K, min(4096, Xtr.shape[0]))
     ctx = _lib.AEContext(Dobs, Denc, Dz, Ddec, otype=otype, act=_act_name(f), s2=s2, eta=inf.eta, max_batch=mb,
-                         device=device, latent=latent)
+                         device=device, latent=latent, iw_samples=iw_samples)
     ctx.set_data(Xtr)
     ctx.set_params(np.concatenate([t.ravel() for t in theta0]))
     offs = np.cumsum([0] + [int(np.prod(s)) for _, s in shapes])
@@ -130,7 +131,7 @@ def ConstructAE(Xtr, Denc=(500,), Dz=20, Ddec=(500,), f="tanh", s2=1.0, inf=None
 
 
 def ConstructVAE(Xtr, Denc=(500,), Dz=20, Ddec=(500,), f="tanh", s2=1.0, inf=None, otype="binary", seed=10,
-                 max_batch=None, device=0):
+                 max_batch=None, device=0, iw_samples=1):
     """ConstructAE with a Gaussian latent: the same five return values, theta in the order
     [..., Wzmu, Wzlv, bzmu, bzlv, ...].  train(idx) takes one AdaGrad step on the ELBO of the
     rows Xtr[idx] (one Philox draw per row and latent, keyed by `seed`, the dataset row and the
@@ -139,14 +140,17 @@ def ConstructVAE(Xtr, Denc=(500,), Dz=20, Ddec=(500,), f="tanh", s2=1.0, inf=Non
     train.marginal_ll(X, K, rows=False) the K-sample importance-weighted estimate of
     sum_i log p(x_i) with the encoder as the proposal (forward only; rows=True: (sum, per-row
     values) -- the figure that ranks a deep model against the one-hidden-layer VAEB's
-    marginal_likelihood)."""
-    ctx, theta = _construct("gauss", Xtr, Denc, Dz, Ddec, f, s2, inf, otype, max_batch, device)
+    marginal_likelihood).  iw_samples = K >= 2: train(idx) steps on the K-sample importance-weighted
+    bound instead (K draws per row, sample stream k) and returns that bound / len(idx); a step needs
+    K * len(idx) <= max_batch, which defaults to max(100 K, min(4096, N)).  train.iw_samples is K."""
+    ctx, theta = _construct("gauss", Xtr, Denc, Dz, Ddec, f, s2, inf, otype, max_batch, device, iw_samples)
     ctx.set_eps_mode(_lib.EPS_PHILOX, seed)
 
     def train(idx):
         return ctx.train(np.asarray(idx, np.int32))
 
     train.ctx = ctx
+    train.iw_samples = ctx.iw_samples
     train.elbo = lambda X: ctx.elbo(_values(X))
     train.marginal_ll = lambda X, K, rows=False: ctx.marginal_ll(_values(X), K, rows=rows)
     return train, ctx.reconstruct, ctx.encode, ctx.decode, theta

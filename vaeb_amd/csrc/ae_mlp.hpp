@@ -16,6 +16,10 @@
 //                         -KL partials 1/2 (1 + lv - mu^2 - e^lv)      PAeFwd (mode LATENT, 2 heads)
 //                         dz = dout W^T, dmu = dz - mu,
 //                         dlv = 1/2 dz (z - mu) + 1/2 (1 - e^lv)       PAeBwd (mode LATENT)
+//   importance-weighted training (iw_samples = K >= 2, ae_iwae.hpp): the decoder on K M stacked
+//                         rows, output deltas scaled by the normalised weights wn, then
+//                         dmu_k = dz - wn z, dlv_k = 1/2 (dz - wn z)(z - mu) + 1/2 wn
+//                                                               PAeBwdT<true> (mode LATENT_IW)
 //   weight gradients:     [in | 1]^T dout (ones row = bias gradient), prior -theta/s2 and
 //                         AdaGrad (infalg.py:155-161) in the epilogue   PAeWgrad
 // The first layer's A operand is gathered on the fly through idx (no copy of Xtr[idx]).
@@ -29,7 +33,7 @@ namespace ae {
 
 enum : int { ACT_TANH = 0, ACT_SIGMOID = 1, ACT_RELU = 2 };
 enum : int { F_ACT = 0, F_LINEAR = 1, F_OUT_BIN = 2, F_OUT_CONT = 3, F_LATENT = 4 };
-enum : int { B_DACT = 0, B_ZPRIOR = 1, B_LATENT = 2 };
+enum : int { B_DACT = 0, B_ZPRIOR = 1, B_LATENT = 2, B_LATENT_IW = 3 };
 enum : int { NOISE_ZERO = 0, NOISE_HOST = 1, NOISE_PHILOX = 2 };   // eps of the F_LATENT epilogue
 constexpr float kEpsLog = 1e-7f;   // logpdf.py:86
 constexpr float kHalfLog2Pi = 0.91893853320467274178f;
@@ -166,14 +170,23 @@ struct PAeFwd {
 // din[M x N] = [dout | dout2] [W | W2]^T  (K = K1 or 2 K1), then * f'(h) or - h (Z prior).
 // B_LATENT (the decoder's first layer, N = Dz): dz = dout W^T, h / h2 / h3 = mu / lv / z,
 // din = dmu = dz - mu, din2 = dlv = 1/2 dz (z - mu) + 1/2 (1 - e^lv).
-struct PAeBwd {
+// B_LATENT_IW (training on the importance-weighted bound, ae_iwae.hpp): M = K * Mp stacked rows,
+// dout already carries the normalised weight wn of its row; stacked row g reads mu / lv at row
+// g mod Mp and z / wn at g:  u = dz - wn z,  din = dmu_k = u,  din2 = dlv_k = 1/2 u (z - mu) + 1/2 wn
+// (no analytic KL: the latent term of log w is differentiated as it stands).  The branch and its
+// two arguments exist only in PAeBwdT<true>, so PAeBwd's kernels and kernel arguments are what
+// they were without it.
+template <bool IW> struct AeBwdIwArgs {};
+template <> struct AeBwdIwArgs<true> { const float* wt; int Mp; };   // wn [M], rows per sample plane
+template <bool IW>
+struct PAeBwdT : AeBwdIwArgs<IW> {
     Dbg a;
     int M, N, K;
     const float *dout, *dout2; int K1;
     const float *W, *W2;             // [N x K1] each (row n = this layer's input unit)
     const float* h; int mode, act;   // h [M x N]: activation (DACT) or Z (ZPRIOR)
     float* din;
-    const float *h2, *h3; float* din2;   // B_LATENT only
+    const float *h2, *h3; float* din2;   // B_LATENT / B_LATENT_IW only
     rsrc_t bd, bd2, bw, bw2;
     DEV void prepare() {
         bd = mkbuf(dout, (int64_t)M * K1 * 4);
@@ -215,6 +228,16 @@ struct PAeBwd {
         for (int r = 0; r < 4; ++r) {
             const int m = m0 + 4 * (lane >> 4) + r;
             if (m >= M) continue;
+            if constexpr (IW) {
+                if (mode == B_LATENT_IW) {
+                    const int64_t o = (int64_t)m * N + n, om = (int64_t)(m % this->Mp) * N + n;
+                    const float w = this->wt[m], z = h3[o], mu = h[om];
+                    const float u = acc[0][r] - w * z;
+                    din[o] = u;
+                    din2[o] = 0.5f * u * (z - mu) + 0.5f * w;
+                    continue;
+                }
+            }
             const float hv = h[(int64_t)m * N + n];
             if (mode == B_LATENT) {
                 const float dz = acc[0][r], lv = h2[(int64_t)m * N + n], z = h3[(int64_t)m * N + n];
@@ -226,6 +249,7 @@ struct PAeBwd {
         }
     }
 };
+using PAeBwd = PAeBwdT<false>;
 
 // ---------------------------------------------------------------- weight gradient + AdaGrad
 // C[Kin + 1 x N] = [in | 1]^T dout over the M batch rows (row Kin = the bias gradient),

@@ -25,6 +25,10 @@ struct vaeb_ae {
     // (max, sum) [2 max_batch], row values [max_batch]; the observation row of each stacked row
     float* iw = nullptr;
     int* iw_yrow = nullptr;
+    // training on the importance-weighted bound (c.iw_samples >= 2; allocated at create):
+    // normalised weights [max_batch], row values [max_batch], log w / exp scratch [max_batch]
+    float *iw_wt = nullptr, *iw_val = nullptr;
+    double* iw_lw = nullptr;
     int eps_mode = VAEB_EPS_PHILOX;
     uint64_t seed = 0;
     int64_t step = 0;                 // Philox step counter
@@ -37,6 +41,17 @@ namespace {
 int ae_alloc(float** p, int64_t n) { return dalloc(p, (size_t)std::max<int64_t>(n, 1)); }
 
 bool ae_gauss(const vaeb_ae* a) { return a->c.latent == VAEB_AE_LATENT_GAUSS; }
+bool ae_iw(const vaeb_ae* a) { return a->c.iw_samples >= 2; }
+
+// vaeb_ae_marginal_ll's and the importance-weighted step's scratch, sized by max_batch
+int ae_iw_scratch(vaeb_ae* a) {
+    const int64_t B = a->c.max_batch;
+    if (!a->iw)
+        if (int rc = ae_alloc(&a->iw, 4 * B)) return rc;
+    if (!a->iw_yrow)
+        if (int rc = dalloc(&a->iw_yrow, (size_t)B)) return rc;
+    return 0;
+}
 
 // eps of one latent forward (ae::PAeFwd F_LATENT): zero (the deterministic predictions),
 // rows of the pushed host eps, or Philox keyed by rows[m] / row0 + m, the step and the domain.
@@ -154,13 +169,17 @@ int ae_wgrad(vaeb_ae* a, const float* in, int in_rows, const int* idx, int Kin, 
     return 0;
 }
 
+template <bool IW = false>
 int ae_bwd(vaeb_ae* a, const float* dout, const float* dout2, int K1, const float* W, const float* W2, int N, int M,
            const float* h, int mode, float* din) {
-    ae::PAeBwd p{};
+    ae::PAeBwdT<IW> p{};
     p.M = M; p.N = N; p.K = dout2 ? 2 * K1 : K1;
     p.dout = dout; p.dout2 = dout2; p.K1 = K1; p.W = W; p.W2 = W2;
     p.h = h; p.mode = mode; p.act = a->c.act; p.din = din;
-    if (mode == ae::B_LATENT) { p.h = a->mu; p.h2 = a->lv; p.h3 = a->Z; p.din = a->dmu; p.din2 = a->dlv; }
+    if (mode == ae::B_LATENT || mode == ae::B_LATENT_IW) {
+        p.h = a->mu; p.h2 = a->lv; p.h3 = a->Z; p.din = a->dmu; p.din2 = a->dlv;
+    }
+    if constexpr (IW) { p.wt = a->iw_wt; p.Mp = M / a->c.iw_samples; }
     launch_bigk<1>(a->s, p);
     CHECK_LAUNCH();
     return 0;
@@ -209,6 +228,68 @@ int ae_step(vaeb_ae* a, const int* idx, int M, int slot, const AeNoise& nz = AeN
         if (int rc = ae_wgrad(a, a->H[ne], M, nullptr, a->de[ne], a->dZ, g.Dz, M, a->oWz, a->obz)) return rc;
     }
     // encoder layers (top down); no data gradient into X
+    for (int i = ne - 1; i >= 0; --i) {
+        if (i > 0)
+            if (int rc = ae_bwd(a, a->dH[i + 1], nullptr, a->de[i + 1], a->theta + a->oWe[i], nullptr, a->de[i], M,
+                                a->H[i], ae::B_DACT, a->dH[i])) return rc;
+        const float* in = (i == 0) ? a->data : a->H[i];
+        if (int rc = ae_wgrad(a, in, i == 0 ? (int)a->nrows : M, i == 0 ? idx : nullptr, a->de[i], a->dH[i + 1],
+                              a->de[i + 1], M, a->oWe[i], a->obe[i])) return rc;
+    }
+    return 0;
+}
+
+// train(idx) on the K-sample importance-weighted bound (c.iw_samples = K >= 2, ae_iwae.hpp): the
+// encoder once on the M rows, the decoder forward and backward on the K * M stacked rows
+// (g = k * M + m) with the output deltas scaled by the normalised weights, the K planes of
+// dmu / dlv summed, then the encoder's backward on M rows as in ae_step.  L_K / M -> outs[slot].
+// lb: the step's offset in the call's idx list of n rows (host eps: sample k of list position i
+// at row k * n + i).
+int ae_step_iw(vaeb_ae* a, const int* idx, int M, int slot, int64_t lb, int64_t n, int64_t step) {
+    const vaeb_ae_config& g = a->c;
+    const int ne = g.n_enc, nd = g.n_dec, D = g.Dobs, K = g.iw_samples, KM = K * M;
+    const bool cont = g.otype == VAEB_AE_CONT;
+    if (int rc = ae_forward(a, a->data, (int)a->nrows, idx, M, false, true, nullptr)) return rc;   // mu, lv
+    ae::AeIwArgs q{};
+    q.Dz = g.Dz; q.R = M; q.S = K; q.k0 = 0; q.row0 = lb; q.n = n;
+    q.eps_mode = a->eps_mode == VAEB_EPS_HOST ? 1 : 0;
+    q.seed = a->seed; q.step = step; q.eps_in = a->eps_in;
+    q.mu = a->mu; q.lv = a->lv; q.z = a->Z; q.lat = a->iw; q.yrow = a->iw_yrow; q.idx = idx;
+    hipLaunchKernelGGL(ae::ae_iw_sample_kernel, dim3(cdiv(KM, 16)), dim3(256), 0, a->s, q);
+    CHECK_LAUNCH();
+    if (int rc = ae_forward(a, a->data, (int)a->nrows, a->iw_yrow, KM, true, false, a->Z)) return rc;
+    ae::AeIwWeightArgs w{};
+    w.M = M; w.K = K; w.D = D; w.nct = cdiv(D, 16); w.logK = std::log((double)K);
+    w.llpart = a->ll; w.lat = a->iw; w.lw = a->iw_lw; w.wt = a->iw_wt; w.rowval = a->iw_val;
+    w.dA = a->dA; w.dA2 = cont ? a->dA2 : nullptr;
+    hipLaunchKernelGGL(ae::ae_iw_weight_kernel, dim3(M), dim3(256), 0, a->s, w);
+    CHECK_LAUNCH();
+    hipLaunchKernelGGL(ae::ae_loglik_kernel, dim3(1), dim3(256), 0, a->s, a->iw_val, (int64_t)M, M, a->outs, slot);
+    CHECK_LAUNCH();
+    // output layer and decoder on the stacked rows
+    const int Hd = a->dd[nd];
+    if (int rc = ae_bwd(a, a->dA, cont ? a->dA2 : nullptr, D, a->theta + a->oWo, cont ? a->theta + a->oWl : nullptr,
+                        Hd, KM, a->G[nd], ae::B_DACT, a->dG[nd])) return rc;
+    if (int rc = ae_wgrad(a, a->G[nd], KM, nullptr, Hd, a->dA, D, KM, a->oWo, a->obo)) return rc;
+    if (cont)
+        if (int rc = ae_wgrad(a, a->G[nd], KM, nullptr, Hd, a->dA2, D, KM, a->oWl, a->obl)) return rc;
+    for (int i = nd - 1; i >= 0; --i) {
+        const float* hin = (i == 0) ? a->Z : a->G[i];
+        if (int rc = i == 0 ? ae_bwd<true>(a, a->dG[1], nullptr, a->dd[1], a->theta + a->oWd[0], nullptr, a->dd[0], KM,
+                                           hin, ae::B_LATENT_IW, nullptr)
+                            : ae_bwd(a, a->dG[i + 1], nullptr, a->dd[i + 1], a->theta + a->oWd[i], nullptr, a->dd[i], KM,
+                                     hin, ae::B_DACT, a->dG[i])) return rc;
+        if (int rc = ae_wgrad(a, hin, KM, nullptr, a->dd[i], a->dG[i + 1], a->dd[i + 1], KM, a->oWd[i], a->obd[i]))
+            return rc;
+    }
+    hipLaunchKernelGGL(ae::ae_iw_plane_sum_kernel, dim3(cdiv(M * g.Dz, 256)), dim3(256), 0, a->s, a->dmu, a->dlv, M,
+                       g.Dz, K);
+    CHECK_LAUNCH();
+    // the two heads and the encoder on the M rows, as ae_step
+    if (int rc = ae_bwd(a, a->dmu, a->dlv, g.Dz, a->theta + a->oWz, a->theta + a->oWzl, a->de[ne], M, a->H[ne],
+                        ae::B_DACT, a->dH[ne])) return rc;
+    if (int rc = ae_wgrad(a, a->H[ne], M, nullptr, a->de[ne], a->dmu, g.Dz, M, a->oWz, a->obz)) return rc;
+    if (int rc = ae_wgrad(a, a->H[ne], M, nullptr, a->de[ne], a->dlv, g.Dz, M, a->oWzl, a->obzl)) return rc;
     for (int i = ne - 1; i >= 0; --i) {
         if (i > 0)
             if (int rc = ae_bwd(a, a->dH[i + 1], nullptr, a->de[i + 1], a->theta + a->oWe[i], nullptr, a->de[i], M,
@@ -290,6 +371,10 @@ int vaeb_ae_create(const vaeb_ae_config* cfg, vaeb_ae** out) {
     if (g.latent != VAEB_AE_LATENT_POINT && g.latent != VAEB_AE_LATENT_GAUSS)
         return fail(VAEB_ERR_ARG, "latent must be VAEB_AE_LATENT_POINT | VAEB_AE_LATENT_GAUSS (got %d)", g.latent);
     if (!(g.s2 > 0.f) || !(g.eta > 0.f)) return fail(VAEB_ERR_ARG, "s2 and eta must be > 0");
+    if (g.iw_samples < 0 || g.iw_samples > (1 << 20))
+        return fail(VAEB_ERR_ARG, "iw_samples = %d: 0 to 2^20 (the Philox sample-stream field)", g.iw_samples);
+    if (g.iw_samples >= 2 && g.latent != VAEB_AE_LATENT_GAUSS)
+        return fail(VAEB_ERR_ARG, "iw_samples = %d needs a VAEB_AE_LATENT_GAUSS context", g.iw_samples);
     auto* a = new vaeb_ae();
     a->c = g;
     if (hipSetDevice(g.device) != hipSuccess || hipStreamCreateWithFlags(&a->s, hipStreamNonBlocking) != hipSuccess) {
@@ -359,6 +444,12 @@ int vaeb_ae_create(const vaeb_ae_config* cfg, vaeb_ae** out) {
         rc = rc ? rc : ae_alloc(&a->kl, B * cdiv(g.Dz, 16));
         rc = rc ? rc : dalloc(&a->esum, 1);
     }
+    if (ae_iw(a)) {
+        rc = rc ? rc : ae_iw_scratch(a);
+        rc = rc ? rc : ae_alloc(&a->iw_wt, B);
+        rc = rc ? rc : ae_alloc(&a->iw_val, B);
+        rc = rc ? rc : dalloc(&a->iw_lw, (size_t)B);
+    }
     rc = rc ? rc : ae_reserve(a, (int)B, 1);
     if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(VAEB_ERR_HIP, "device init failed");
     if (rc) { vaeb_ae_destroy(a); return rc; }
@@ -370,12 +461,13 @@ int vaeb_ae_destroy(vaeb_ae* a) {
     if (!a) return 0;
     if (a->s) hipStreamSynchronize(a->s);
     std::vector<float*> ps = {a->theta, a->acc, a->data, a->Z, a->dZ, a->Xpr, a->ls2, a->dA, a->dA2, a->ll, a->outs,
-                              a->xin, a->mu, a->lv, a->dmu, a->dlv, a->kl, a->eps_in, a->iw};
+                              a->xin, a->mu, a->lv, a->dmu, a->dlv, a->kl, a->eps_in, a->iw, a->iw_wt, a->iw_val};
     for (auto* v : {&a->H, &a->G, &a->dH, &a->dG}) ps.insert(ps.end(), v->begin(), v->end());
     for (float* p : ps) if (p) hipFree(p);
     if (a->idx) hipFree(a->idx);
     if (a->iw_yrow) hipFree(a->iw_yrow);
     if (a->esum) hipFree(a->esum);
+    if (a->iw_lw) hipFree(a->iw_lw);
     if (a->s) hipStreamDestroy(a->s);
     delete a;
     return 0;
@@ -406,15 +498,21 @@ int vaeb_ae_train_many(vaeb_ae* a, const int32_t* idx, int32_t n, int32_t batch,
     if (!a || !idx || !out || n <= 0 || batch <= 0) return fail(VAEB_ERR_ARG, "bad arguments");
     if (batch > a->c.max_batch) return fail(VAEB_ERR_ARG, "batch %d > max_batch %d", batch, a->c.max_batch);
     if (int rc = ae_check_idx(a, idx, n)) return rc;
-    const bool gauss = ae_gauss(a);
+    const bool gauss = ae_gauss(a), iw = ae_iw(a);
+    if (iw && (int64_t)a->c.iw_samples * std::min(batch, n) > a->c.max_batch)
+        return fail(VAEB_ERR_ARG, "iw_samples %d x batch %d > max_batch %d (the stacked sample planes)",
+                    a->c.iw_samples, std::min(batch, n), a->c.max_batch);
     if (gauss)
-        if (int rc = ae_host_eps_ready(a, n)) return rc;
+        if (int rc = ae_host_eps_ready(a, iw ? (int64_t)a->c.iw_samples * n : (int64_t)n)) return rc;
     const int nb = cdiv(n, batch);
     if (int rc = ae_reserve(a, n, nb)) return rc;
     HIP_TRY(hipMemcpyAsync(a->idx, idx, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, a->s));
     for (int j = 0; j < nb; ++j) {
         const int lb = j * batch, m = std::min(batch, n - lb);
-        if (gauss) {   // each step draws at the counter, then advances it
+        if (iw) {
+            if (int rc = ae_step_iw(a, a->idx + lb, m, j, lb, n, a->step)) return rc;
+            ++a->step;
+        } else if (gauss) {   // each step draws at the counter, then advances it
             if (int rc = ae_step(a, a->idx + lb, m, j, ae_noise(a, a->idx + lb, lb, a->step, false))) return rc;
             ++a->step;
         } else if (int rc = ae_step(a, a->idx + lb, m, j)) return rc;
@@ -532,10 +630,7 @@ int vaeb_ae_marginal_ll(vaeb_ae* a, const float* x, int64_t n, int32_t K, double
     if (int rc = ae_host_eps_ready(a, n * K)) return rc;
     const vaeb_ae_config& g = a->c;
     const int B = g.max_batch, nct = cdiv(g.Dobs, 16);
-    if (!a->iw)
-        if (int rc = ae_alloc(&a->iw, 4 * (int64_t)B)) return rc;
-    if (!a->iw_yrow)
-        if (int rc = dalloc(&a->iw_yrow, (size_t)B)) return rc;
+    if (int rc = ae_iw_scratch(a)) return rc;
     IwArgs w{};
     w.nctD = nct; w.K = K; w.logK = (float)std::log((double)K);
     w.lat = a->iw; w.ms = a->iw + B; w.rows = a->iw + 3 * (int64_t)B; w.lp_part = a->ll;
