@@ -43,10 +43,18 @@ enum vaeb_dtype     { VAEB_DTYPE_F32 = 0,      /* fp32 MFMA, the reference's flo
                                                   a power of two ~ B_global (undone in fp32) */
 enum vaeb_status    { VAEB_OK = 0, VAEB_ERR_ARG = -1, VAEB_ERR_HIP = -2, VAEB_ERR_STATE = -3,
                       VAEB_ERR_COMM = -4, VAEB_ERR_NOMEM = -5,
-                      VAEB_ERR_NUMERIC = -6 };  /* a step's values left the fixed-point latent hand-off's
-                                                   range (NaN / inf / |partial| >= 2^17): those latent
-                                                   values were set to NaN; reported by the next
-                                                   vaeb_update / vaeb_epoch_elbo, then cleared */
+                      VAEB_ERR_NUMERIC = -6 };  /* a step's values left a range the engine depends on;
+                                                   reported by the next vaeb_update /
+                                                   vaeb_epoch_elbo, then cleared.  Either (fp32
+                                                   engine) the fixed-point latent hand-off's range
+                                                   (NaN / inf / |partial| >= 2^17): those latent
+                                                   values were set to NaN; or (VAEB_DTYPE_F16) the
+                                                   fp16 range: a training step stored z, dA2 | dA6,
+                                                   dA1, [dMu | dLv] or dA3 outside +-65504 (or NaN /
+                                                   inf) -- theta and the Adagrad state after that
+                                                   step are not usable: restore them (vaeb_set_params,
+                                                   vaeb_set_adagrad_state, a checkpoint) or train with
+                                                   VAEB_DTYPE_BF16.  vaeb_last_error names which. */
 
 typedef struct vaeb_config {
     int32_t D;            /* input size (784 MNIST, 560 Frey)                         */

@@ -21,6 +21,16 @@ float h16_scale(const vaeb_ctx* c) {
     return std::ldexp(1.f, e2 - 1);
 }
 
+// fp16: the guard word that a training step's range-checked 16-bit stores report to
+// (h16_engines.hpp, H16_GUARD_FIELD); the bf16 structs have no such member.
+template <class E>
+E h16_guarded(vaeb_ctx* c, E e, bool train = true) {
+    if constexpr (kF16) {
+        if (train) e.guard = c->blk + kBlkFxErr;
+    }
+    return e;
+}
+
 // Block-tile width for an M x N product: 256-wide tiles unless that leaves the chip
 // (256 CUs, one block each) less than full.
 int bf_bn(int M, int N) { return cdiv(M, bf::BM) * cdiv(N, 256) >= 256 ? 256 : 128; }
@@ -335,7 +345,7 @@ int bf_forward(vaeb_ctx* c, int par, const BfFwd& f, Prof& pr) {
         eh.eps_in = f.eps_in; eh.eps_in_ld = f.eps_in_ld;
         eh.rows = f.xb; eh.row_base_mul = f.row_base_mul; eh.row_base_add = f.row_base_add;
         pr.mark(K_BF_HEADS);
-        REP(pr) if (int rc = bf_thin<bf::KO, 64>(s, ta, dim3(cdiv(M, 64), Z / 64), eh)) return rc;
+        REP(pr) if (int rc = bf_thin<bf::KO, 64>(s, ta, dim3(cdiv(M, 64), Z / 64), h16_guarded(c, eh, f.train))) return rc;
     } else {
     // heads: [mu | lv] split-K slabs
     const int ksh = bf_slices(H, b.ks_heads);
@@ -352,6 +362,7 @@ int bf_forward(vaeb_ctx* c, int par, const BfFwd& f, Prof& pr) {
     la.eps_mode = c->eps_mode == VAEB_EPS_HOST ? 1 : 0; la.seed = c->seed; la.step = c->step; la.domain = f.domain;
     la.eps_in = f.eps_in; la.eps_in_ld = f.eps_in_ld;
     la.rows = f.xb; la.row_base_mul = f.row_base_mul; la.row_base_add = f.row_base_add;
+    la = h16_guarded(c, la, f.train);
     pr.mark(K_BF_LATENT);
     if (bf_lat4(c, la)) REP(pr) hipLaunchKernelGGL(bf::latent_fwd_v4_kernel, dim3(cdiv(M, 8)), dim3(256), 0, s, la);
     else REP(pr) hipLaunchKernelGGL(bf::latent_fwd_kernel, dim3(cdiv(M, 4)), dim3(256), 0, s, la);
@@ -369,7 +380,9 @@ int bf_forward(vaeb_ctx* c, int par, const BfFwd& f, Prof& pr) {
     // (dA is stored with the backward's loss scale: the fp16 mean objective, h16_scale)
     const float sl = lsc / (float)L * (f.train ? h16_scale(c) : 1.f);
     if (gs) {
-        bf::EpiDecOut<true> e{b2, b6, f.x, D, M, LM, Dn, D, f.train ? 1 : 0, sl, f.xb, b.dA, Dn, b.lp, nlp, b.cp26, f.yout};
+        const bf::EpiDecOut<true> e = h16_guarded(
+            c, bf::EpiDecOut<true>{b2, b6, f.x, D, M, LM, Dn, D, f.train ? 1 : 0, sl, f.xb, b.dA, Dn, b.lp, nlp, b.cp26, f.yout},
+            f.train);
         REP(pr) if (int rc = bf_gemm<bf::KC, bf::KO>(s, b.hd, H, (int64_t)LM * H * 2, sh + b.s26, Dn,
                                                       (int64_t)H * Dn * 2, LM, Dn, H, 1, e)) return rc;
     } else {
@@ -379,14 +392,17 @@ int bf_forward(vaeb_ctx* c, int par, const BfFwd& f, Prof& pr) {
             // tiles, one block per CU (the 256 x 128 two-block form spilled 76 B per lane: 747.6 /
             // 752.2 / 750.4 -> 741.4 / 744.3 / 744.1 us per step, profiles/r5/synth_ab.txt; its
             // switch VAEB_BF_DECT was removed in round 6)
-            bf::EpiDecOutT e{b2, f.x, D, M, LM, D, f.train ? 1 : 0, sl, f.xb, b.dA, Dn, b.lp, nlp, b.cp26, f.yout,
-                             f.xbits};
+            const bf::EpiDecOutT e = h16_guarded(
+                c, bf::EpiDecOutT{b2, f.x, D, M, LM, D, f.train ? 1 : 0, sl, f.xb, b.dA, Dn, b.lp, nlp, b.cp26, f.yout, f.xbits},
+                f.train);
             bf::GemmArgs gg = bf_args256(sh + b.s26, Dn, (int64_t)H * Dn * 2, b.hd, H, (int64_t)LM * H * 2, Dn, LM, H);
             REP(pr) if (int rc = bf_launch8<bf::KO, bf::KC>(s, gg, 1, e)) return rc;
         } else {
         // D % 8 != 0: on hd W2, 256 x 128 tiles, 3-stage ring, two blocks per CU (one block's
         // likelihood epilogue beside the other's main loop)
-        bf::EpiDecOut<false> e{b2, b6, f.x, D, M, LM, Dn, D, f.train ? 1 : 0, sl, f.xb, b.dA, Dn, b.lp, nlp, b.cp26, f.yout};
+        const bf::EpiDecOut<false> e = h16_guarded(
+            c, bf::EpiDecOut<false>{b2, b6, f.x, D, M, LM, Dn, D, f.train ? 1 : 0, sl, f.xb, b.dA, Dn, b.lp, nlp, b.cp26, f.yout},
+            f.train);
         bf::GemmArgs gg = bf_args256(b.hd, H, (int64_t)LM * H * 2, sh + b.s26, Dn, (int64_t)H * Dn * 2, LM, Dn, H);
         gg.tiles_n = cdiv(Dn, 128);
         REP(pr) if (int rc = bf_launch<bf::KC, bf::KO, 128, bf::EpiDecOut<false>, 3>(s, gg, 1, e)) return rc;
@@ -466,7 +482,7 @@ int bf_train_step(vaeb_ctx* c, int par, bool prof, int direct) {
     // dhd: dA1 = ([dA2 | dA6] [W2 | W6]^T) (1 - hd^2)  and  dW2 (| dW6) = hd^T [dA2 | dA6] ->
     // optimizer: both need only the decoder's outputs; unforked (DP, profiling, VAEB_BF_FORK=0)
     // they share one grid of 256 x 256 tiles (bf_gemm2)
-    const bf::EpiDTanh e_dhd{b.hd, H, LM, H, b.dA1, H, b.cp1};
+    const bf::EpiDTanh e_dhd = h16_guarded(c, bf::EpiDTanh{b.hd, H, LM, H, b.dA1, H, b.cp1});
     bf::Opt o26 = opt;
     o26.shadow_out = b.shadow2[par ^ 1] + b.s26;
     bf::EpiAdagrad e_w26{cmap(gs ? 2 : 0, 0, c->off[sl.W2], gs ? c->off[sl.W6] : 0, D, D), o26, H, Dn};
@@ -486,12 +502,13 @@ int bf_train_step(vaeb_ctx* c, int par, bool prof, int direct) {
         pr.mark(K_BF_DHD);
         if (dzf) {
             // ... and dZ as split-K slabs from the dA1 tile in LDS (EpiDTanhTDz, VAEB_BF_DZFUSE)
-            const bf::EpiDTanhTDz e{{b.hd, H, LM, H, b.dA1, H, b.cp1}, sh + b.s1, Z, H, b.dz_slab, (int64_t)LM * Z};
+            const bf::EpiDTanhTDz e =
+                h16_guarded(c, bf::EpiDTanhTDz{{b.hd, H, LM, H, b.dA1, H, b.cp1}, sh + b.s1, Z, H, b.dz_slab, (int64_t)LM * Z});
             const bf::GemmArgs g1 = bf_args256(sh + b.s26, Dn, (int64_t)H * Dn * 2, b.dA, Dn, (int64_t)LM * Dn * 2, H, LM, Dn);
             REP(pr) if (int rc = bf_launch8<bf::KC, bf::KC>(s, g1, 1, e)) return rc;
         } else if (c->bf_dtt && H % 8 == 0) {
             // the transposed product dA1^T = W2 dA^T (EpiDTanhT: 8-byte LDS epilogue accesses)
-            const bf::EpiDTanhT e{b.hd, H, LM, H, b.dA1, H, b.cp1};
+            const bf::EpiDTanhT e = h16_guarded(c, bf::EpiDTanhT{b.hd, H, LM, H, b.dA1, H, b.cp1});
             REP(pr) if (int rc = bf_gemm<bf::KC, bf::KC>(s, sh + b.s26, Dn, (int64_t)H * Dn * 2, b.dA, Dn,
                                                           (int64_t)LM * Dn * 2, H, LM, Dn, 1, e)) return rc;
         } else {
@@ -562,6 +579,7 @@ int bf_train_step(vaeb_ctx* c, int par, bool prof, int direct) {
     la.sc = ((g.objective == VAEB_OBJ_MEAN_MAP) ? 1.0f / (float)g.B_global : 1.0f) * h16_scale(c);
     la.mu = b.mu; la.lv = b.lv; la.eps = b.eps;
     la.dz_slab = b.dz_slab; la.ndz = ksz; la.dmulv = b.dml; la.colpart = b.cp45;
+    la = h16_guarded(c, la);
     pr.mark(K_BF_LATENT_BWD);
     if (dzf) {
         // the dhd blocks stored dZ as cdiv(H, 256) split-K slabs: the latent backward sums them
@@ -577,7 +595,7 @@ int bf_train_step(vaeb_ctx* c, int par, bool prof, int direct) {
         bf::EpiDzLatent ez{};
         ez.mu = b.mu; ez.lv = b.lv; ez.eps = b.eps; ez.dmulv = b.dml; ez.colpart = b.cp45;
         ez.sc = la.sc; ez.M = M; ez.Z = Z;
-        REP(pr) if (int rc = bf_thin<bf::KC, 32>(s, ta, dim3(cdiv(M, 32), Z / 128), ez)) return rc;
+        REP(pr) if (int rc = bf_thin<bf::KC, 32>(s, ta, dim3(cdiv(M, 32), Z / 128), h16_guarded(c, ez))) return rc;
     } else if (bf_lat4(c, la))
         REP(pr) hipLaunchKernelGGL(bf::latent_bwd_v4_kernel, dim3(cdiv(M, bf::kLbRows), cdiv(Z, 128)), dim3(256), 0, s, la);
     else
@@ -593,11 +611,11 @@ int bf_train_step(vaeb_ctx* c, int par, bool prof, int direct) {
         // the transposed product dA3^T = [W4 | W5] [dMu | dLv]^T (EpiDTanhT)
         REP(pr) if (int rc = bf_gemm<bf::KC, bf::KC>(s, sh + b.s45, 2 * Z, (int64_t)H * 2 * Z * 2, b.dml, 2 * Z,
                                                       (int64_t)M * 2 * Z * 2, H, M, 2 * Z, 1,
-                                                      bf::EpiDTanhT{b.h, H, M, H, b.dA3, H, b.cp3})) return rc;
+                                                      h16_guarded(c, bf::EpiDTanhT{b.h, H, M, H, b.dA3, H, b.cp3}))) return rc;
     } else {
         REP(pr) if (int rc = bf_gemm<bf::KC, bf::KC>(s, b.dml, 2 * Z, (int64_t)M * 2 * Z * 2, sh + b.s45, 2 * Z,
                                                       (int64_t)H * 2 * Z * 2, M, H, 2 * Z, 1,
-                                                      bf::EpiDTanh{b.h, H, M, H, b.dA3, H, b.cp3})) return rc;
+                                                      h16_guarded(c, bf::EpiDTanh{b.h, H, M, H, b.dA3, H, b.cp3}))) return rc;
     }
     // dW4 | dW5 = h^T [dMu | dLv] (split-K slabs) -> optimizer
     {

@@ -86,6 +86,15 @@ typedef _Float16 bf16x2_t __attribute__((ext_vector_type(2)));
 DEV uint32_t f2bf(float f) { return __builtin_bit_cast(uint16_t, (_Float16)f); }
 DEV float bf2f(uint32_t b) { return (float)__builtin_bit_cast(_Float16, (uint16_t)b); }
 DEV f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
+// The range guard of the backward's and z's 16-bit stores (h16_engines.hpp H16_CHECK / H16_REPORT):
+// a lane that converted a value outside +-65504 (or NaN / inf) sets kStF16Range in the control
+// block's guard word (an agent-scope atomic OR, as latent.hpp fx_inc sets its bit; the step's
+// ELBO reduction folds the word into the sticky status).  guard == nullptr: not a training step.
+DEV void h16_report(uint64_t* guard, bool bad) {
+    if (__builtin_expect(bad && guard != nullptr, 0))
+        __hip_atomic_fetch_or((__attribute__((address_space(1))) unsigned long long*)guard, kStF16Range,
+                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 #else
 // f32 -> bf16, round to nearest even: gfx950's v_cvt_pk_bf16_f32 (one instruction; the
 // integer form (u + 0x7FFF + ((u >> 16) & 1)) >> 16 gives the same bits for finite inputs in
@@ -530,6 +539,7 @@ struct EpiDTanh {
     const bf16_t* t; int ldt; int M, N;
     bf16_t* out; int ldo;
     float* colpart;
+    H16_GUARD_FIELD
     template <int W>
     DEV void load_in(int m0, int n0, char* smem) const {
         tile_load<W, W>(smem, mkbuf(t, (int64_t)M * ldt * 2), ldt, m0, n0, M, N, 0);
@@ -538,6 +548,7 @@ struct EpiDTanh {
     DEV void apply(int mw, int nw, f32x4 (&acc)[4][4], int, char* smem) const {
         const int lane = threadIdx.x & 63;
         const int lr0 = mw & (BM - 1), lc0 = nw & (W - 1);
+        [[maybe_unused]] bool bad = false;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int col = ecol<CM>(nw, j, lane);
@@ -549,12 +560,14 @@ struct EpiDTanh {
                     const int lr = erow(lr0, i, r, lane), lc = ecol<CM>(lc0, j, lane);
                     const float tv = lds_bf<W>(smem, lr, lc);
                     const float v = acc[i][j][r] * (1.f - tv * tv);
+                    H16_CHECK(bad, v);
                     lds_st_bf<W>(smem, lr, lc, v);
                     cs += (erow(mw, i, r, lane) < M) ? v : 0.f;
                 }
             cs = colsum_lanes(cs);
             if (lane < 16 && col < N) colpart[(int64_t)(mw >> 6) * N + col] = cs;
         }
+        H16_REPORT(*this, bad);
     }
     template <int W>
     DEV void store_out(int m0, int n0, char* smem) const { tile_store<W>(smem, out, ldo, m0, n0, M, N); }
@@ -572,6 +585,7 @@ struct EpiDTanhT {
     const bf16_t* t; int ldt; int M, N;   // output rows, output columns (N % 8 == 0)
     bf16_t* out; int ldo;
     float* colpart;
+    H16_GUARD_FIELD
     static constexpr int kPitch = 528;    // 256 bf16 + 16 B: 132 dwords = 4 (mod 64)
     template <int W>
     DEV void load_in(int m0, int n0, char* smem) const {
@@ -592,6 +606,7 @@ struct EpiDTanhT {
         const int lane = threadIdx.x & 63, q = lane >> 4, li = lane & 15;
         const int lc0 = mw & (BM - 1), lr0 = nw & (W - 1);
         f32x4 cs[4];
+        [[maybe_unused]] bool bad = false;
 #pragma unroll
         for (int i = 0; i < 4; ++i) cs[i] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -608,11 +623,13 @@ struct EpiDTanhT {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     v[r] = acc[i][j][r] * (1.f - tv[r] * tv[r]);
+                    H16_CHECK(bad, v[r]);
                     cs[i][r] += ok ? v[r] : 0.f;
                 }
                 *reinterpret_cast<uint2*>(px) = make_uint2(f2bf2(v[0], v[1]), f2bf2(v[2], v[3]));
             }
         }
+        H16_REPORT(*this, bad);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int col = mw + 16 * i + 4 * q;
@@ -702,6 +719,7 @@ struct EpiDecOut {
     float* lp; int nlp;
     float* colpart;
     float* yout;
+    H16_GUARD_FIELD
     template <int W>
     DEV void load_in(int m0, int n0, char* smem) const {
         const rsrc_t src = mkbuf(x + xb.offset(), (int64_t)Mx * ldx * 2);
@@ -719,6 +737,7 @@ struct EpiDecOut {
         int col[JN], d[JN];
         bool cok[JN];
         float bb2[JN], bb6[JN], cs2[JN], cs6[JN];
+        [[maybe_unused]] bool bad = false;
 #pragma unroll
         for (int j = 0; j < JN; ++j) {
             col[j] = ecol<CM>(nw, j, lane);                               // dA column
@@ -764,9 +783,11 @@ struct EpiDecOut {
                     if (train) {
                         lds_st_bf<W>(smem, lr, ecol<CM>(lc0, j, lane), g2);
                         cs2[j] += ok ? g2 : 0.f;
+                        H16_CHECK(bad, ok ? g2 : 0.f);
                         if constexpr (GAUSS) {
                             lds_st_bf<W>(smem, lr, ecol<CM>(lc0, j, lane) + 32, g6);
                             cs6[j] += ok ? g6 : 0.f;
+                            H16_CHECK(bad, ok ? g6 : 0.f);
                         }
                     }
                 }
@@ -780,6 +801,7 @@ struct EpiDecOut {
                 }
             }
         }
+        H16_REPORT(*this, bad);
         if (train) {
 #pragma unroll
             for (int j = 0; j < JN; ++j) {
@@ -824,6 +846,7 @@ struct EpiDecOutT {
     // a timing-only build without the x fetch put it at ~11 us of config 5's 142-us decoder
     // (profiles/r6/decoder_xpf_ab.txt)
     const uint32_t* xbits;
+    H16_GUARD_FIELD
     // LDS tile [W rows][256 columns] bf16, pitch 528 B = 132 dwords = 4 (mod 64): the 8-byte
     // accesses of a 32-lane group (16 rows x 2 column quads) hit 64 distinct banks
     static constexpr int kPitch = 528;
@@ -878,6 +901,7 @@ struct EpiDecOutT {
         // output row tiles j outermost: the row's log p terms are two running values, the
         // column sums 16 (4 column quads x 4) carried over the row tiles
         f32x4 cs[4];
+        [[maybe_unused]] bool bad = false;
 #pragma unroll
         for (int i = 0; i < 4; ++i) cs[i] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -905,6 +929,7 @@ struct EpiDecOutT {
                     pd *= ok ? dd : 1.f;
                     const float g = sl * (xv - y);
                     cs[i][r] += ok ? g : 0.f;
+                    H16_CHECK(bad, ok ? g : 0.f);
                     if (yout && ok) bst(yb, (uint32_t)(row * D + col + r) * 4u, y);
                     gv[r] = g;
                 }
@@ -915,6 +940,7 @@ struct EpiDecOutT {
             v += __shfl_xor(v, 32, 64);
             if (q == 0 && rok && mw < D) lp[(int64_t)row * nlp + (mw >> 6)] = v;
         }
+        if (train) H16_REPORT(*this, bad);
         if (train) {
             // the column sums of this wave block's 64 rows: 4 row tiles in the lane, then the 16
             // lanes of the column quad

@@ -10,6 +10,9 @@ namespace vaeb {
 // accumulators (double), 2 the sticky step status, 3 the last step's SGVB / B (float), 4
 // the fixed-point hand-off range-guard word, then the hand-off accumulators (latent.hpp).
 constexpr int kBlkStatus = 2, kBlkElbo = 3, kBlkFxErr = 4, kBlkAcc = 5;
+// Bits of the guard word (and of the sticky status it is folded into): the fixed-point hand-off's
+// range guard (latent.hpp fx_inc), and the fp16 engine's 16-bit stores (gemm_bf16.hpp h16_report)
+constexpr unsigned long long kStFxRange = 1ull, kStF16Range = 2ull;
 
 struct ElboArgs {
     const float* lp_part; int64_t n_lp;   // [Me][nctD] per-row log p(x|z) partials

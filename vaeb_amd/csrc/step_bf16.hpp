@@ -75,6 +75,7 @@ struct LatentArgs {
     const float* dz_slab; int ndz;     // [ndz][L*M][Z]
     bf16_t* dmulv;                     // [M][2Z]
     float* colpart;                    // [ceil(M/64)][2Z]
+    H16_GUARD_FIELD
 };
 
 // Fixed-order sum of n fp32 split-K slab values (v[s * stride + off], s = 0..n-1) added to
@@ -108,6 +109,7 @@ __global__ __launch_bounds__(256) void latent_fwd_kernel(LatentArgs a) {
     const uint32_t sstride = (uint32_t)a.M * Z2 * 4u;
     float kl = 0.f;
     float la[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // LA: L <= 8 on this path
+    [[maybe_unused]] bool bad = false;
     for (int j = lane; j < Z; j += 64) {
         const uint32_t o = ((uint32_t)m * Z2 + j) * 4u;
         const float mu = slab_sum(bsl, o, sstride, a.nslab, true, a.b4[j]);
@@ -125,6 +127,7 @@ __global__ __launch_bounds__(256) void latent_fwd_kernel(LatentArgs a) {
             const float z = mu + sd * e;
             const int64_t o = ((int64_t)l * a.M + m) * Z + j;
             a.eps[o] = e;
+            H16_CHECK(bad, z);
             a.z[o] = (bf16_t)f2bf(z);
             if (a.est == EST_LA && l < 8) {
                 // log p(z) - log q(z|x) = -z^2/2 + lv/2 + (z - mu)^2 e^{-lv} / 2
@@ -132,6 +135,7 @@ __global__ __launch_bounds__(256) void latent_fwd_kernel(LatentArgs a) {
             }
         }
     }
+    H16_REPORT(a, bad);
     if (a.est == EST_LA) {
         for (int l = 0; l < a.L && l < 8; ++l) {
             float v = la[l];
@@ -215,16 +219,19 @@ __global__ __launch_bounds__(256) void latent_bwd_kernel(LatentArgs a) {
         }
     }
     float cs = 0.f;
+    [[maybe_unused]] bool bad = false;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         float v;
         if (a.est == EST_LA) v = g[r] + sl * t[r];
         else v = isv ? g[r] + a.sc * 0.5f * (1.f - fexp(lv[r])) : g[r] - a.sc * mu[r];
         if (ok[r]) {
+            H16_CHECK(bad, v);
             a.dmulv[(int64_t)mr[r] * Z2 + c] = (bf16_t)f2bf(v);
             cs += v;
         }
     }
+    H16_REPORT(a, bad);
     red[w][lane] = cs;
     __syncthreads();
     if (w == 0 && cok)
@@ -271,6 +278,7 @@ __global__ __launch_bounds__(256) void latent_fwd_v4_kernel(LatentArgs a) {
     const uint32_t sstride = (uint32_t)a.M * Z2 * 4u;
     float kl = 0.f;
     float la[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // LA: L <= 8 on this path
+    [[maybe_unused]] bool bad = false;
     for (int j = 4 * hl; j < Z; j += 128) {
         const bool ok = rok;
         const uint32_t o = ((uint32_t)m * Z2 + j) * 4u;
@@ -298,7 +306,10 @@ __global__ __launch_bounds__(256) void latent_fwd_v4_kernel(LatentArgs a) {
             }
             f32x4 z;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) z[k] = mu[k] + sd[k] * e[k];
+            for (int k = 0; k < 4; ++k) {
+                z[k] = mu[k] + sd[k] * e[k];
+                H16_CHECK(bad, z[k]);
+            }
             const int64_t oz = ((int64_t)l * a.M + m) * Z + j;
             *reinterpret_cast<f32x4*>(a.eps + oz) = e;
             st_bf16x4(a.z + oz, z);
@@ -308,6 +319,7 @@ __global__ __launch_bounds__(256) void latent_fwd_v4_kernel(LatentArgs a) {
             }
         }
     }
+    H16_REPORT(a, bad);
     // row sums over the 32 lanes of the half-wave
     if (a.est == EST_LA) {
         for (int l = 0; l < a.L && l < 8; ++l) {
@@ -389,6 +401,7 @@ __global__ __launch_bounds__(256) void latent_bwd_v4_kernel(LatentArgs a) {
             }
     }
     f32x4 cm = zero4(), cv = zero4();
+    [[maybe_unused]] bool bad = false;
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
         f32x4 dm, dl;
@@ -403,12 +416,18 @@ __global__ __launch_bounds__(256) void latent_bwd_v4_kernel(LatentArgs a) {
             }
         }
         if (ok[r]) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                H16_CHECK(bad, dm[k]);
+                H16_CHECK(bad, dl[k]);
+            }
             st_bf16x4(a.dmulv + (int64_t)mr[r] * Z2 + j, dm);
             st_bf16x4(a.dmulv + (int64_t)mr[r] * Z2 + Z + j, dl);
             cm += dm;
             cv += dl;
         }
     }
+    H16_REPORT(a, bad);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         red[rs][4 * cl + k] = cm[k];

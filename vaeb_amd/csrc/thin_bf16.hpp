@@ -181,6 +181,7 @@ struct EpiHeadsLatent {
     int eps_mode; uint64_t seed; const int64_t* step; uint32_t domain;
     const float* eps_in; int64_t eps_in_ld;
     BatchRef rows; int64_t row_base_mul, row_base_add;
+    H16_GUARD_FIELD
     struct Pre { float b4[2], b5[2]; };
     DEV static int col(int wc, int j) { return j < 2 ? 32 * wc + 16 * j : 64 + 32 * wc + 16 * (j - 2); }
     DEV Pre prefetch(int, int bn, int, int wc, int lane) const {
@@ -200,6 +201,7 @@ struct EpiHeadsLatent {
         const int64_t brow = rows.order ? (int64_t)rows.order[*rows.cursor] : 0;
         const uint64_t c23 = philox_c23(*step, domain);
         float kl[4] = {0.f, 0.f, 0.f, 0.f};
+        [[maybe_unused]] bool bad = false;
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             const int j = bn * 64 + 32 * wc + 16 * t + li;
@@ -219,9 +221,11 @@ struct EpiHeadsLatent {
                 mu[o] = mv;
                 lv[o] = lvv;
                 eps[o] = e;
+                H16_CHECK(bad, mv + sd * e);
                 z[o] = (bf16_t)f2bf(mv + sd * e);
             }
         }
+        H16_REPORT(*this, bad);
         // the row's KL over this block's 64 latents: the 16 lanes of a row group (DPP), then
         // the two column groups in order
         const int wave = threadIdx.x >> 6;
@@ -248,6 +252,7 @@ struct EpiDzLatent {
     float* colpart;
     float sc;
     int M, Z;
+    H16_GUARD_FIELD
     struct Pre { float mu[2][4], lv[2][4], e[2][4]; };
     DEV static int col(int wc, int j) { return 32 * wc + 16 * j; }
     DEV Pre prefetch(int m0, int bn, int wr, int wc, int lane) const {
@@ -270,6 +275,7 @@ struct EpiDzLatent {
     DEV void apply(const f32x4 (&acc)[2], const Pre& p, int m0, int bn, int wr, int wc, int lane) const {
         const int q = lane >> 4, li = lane & 15;
         const int Z2 = 2 * Z;
+        [[maybe_unused]] bool bad = false;
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             const int j = bn * 128 + 32 * wc + 16 * t + li;
@@ -282,6 +288,8 @@ struct EpiDzLatent {
                 const float dm = dz - sc * p.mu[t][r];
                 const float dl = dz * 0.5f * sd * p.e[t][r] + sc * 0.5f * (1.f - fexp(p.lv[t][r]));
                 if (m < M) {
+                    H16_CHECK(bad, dm);
+                    H16_CHECK(bad, dl);
                     dmulv[(int64_t)m * Z2 + j] = (bf16_t)f2bf(dm);
                     dmulv[(int64_t)m * Z2 + Z + j] = (bf16_t)f2bf(dl);
                     cm += dm;
@@ -299,6 +307,7 @@ struct EpiDzLatent {
                 colpart[(int64_t)rb * Z2 + Z + j] = cv;
             }
         }
+        H16_REPORT(*this, bad);
     }
 };
 

@@ -806,14 +806,26 @@ static int wait_step_result(vaeb_ctx* c) {
     return 0;
 }
 
+// VAEB_ERR_NUMERIC for the bits of a sticky step status (kernels_aux.hpp kStFxRange, kStF16Range);
+// `when`: "the step" / "a step since the last read".
+static int numeric_fail(uint64_t st, const char* when) {
+    if (st & kStF16Range)
+        return fail(VAEB_ERR_NUMERIC, "%s left the fp16 range: a 16-bit operand (z, dA2 | dA6, dA1, [dMu | dLv] or dA3) "
+                                      "outside +-65504, NaN or inf; theta and the Adagrad state after it are not "
+                                      "usable (restore them, or use VAEB_DTYPE_BF16)", when);
+    return fail(VAEB_ERR_NUMERIC, "%s overflowed the fixed-point latent hand-off (a partial outside +-2^17, "
+                                  "NaN or inf): its latent values are NaN", when);
+}
+
 // The sticky step status read at a sync point (kernels_aux.hpp elbo_emit): cleared, and
-// reported as VAEB_ERR_NUMERIC.
+// reported as VAEB_ERR_NUMERIC.  st: the step's flag that the status word is set.
 static int take_status(vaeb_ctx* c, uint64_t st) {
     if (!st) return 0;
+    uint64_t* const h = reinterpret_cast<uint64_t*>(&c->h_d2[3]);
+    HIP_TRY(hipMemcpyAsync(h, c->blk + kBlkStatus, sizeof(uint64_t), hipMemcpyDeviceToHost, c->s));
     HIP_TRY(hipMemsetAsync(c->blk + kBlkStatus, 0, sizeof(uint64_t), c->s));
     HIP_TRY(hipStreamSynchronize(c->s));
-    return fail(VAEB_ERR_NUMERIC, "the step overflowed the fixed-point latent hand-off (a partial outside +-2^17, "
-                                  "NaN or inf): its latent values are NaN");
+    return numeric_fail(*h, "the step");
 }
 
 int vaeb_update(vaeb_ctx* c, int32_t batch_index, float* out) {
@@ -890,9 +902,7 @@ int vaeb_epoch_elbo(vaeb_ctx* c, double* out_sum, int64_t* out_steps) {
     if (out_steps) *out_steps = (int64_t)c->h_d2[1];
     uint64_t st;
     memcpy(&st, &c->h_d2[2], sizeof(st));
-    return st ? fail(VAEB_ERR_NUMERIC, "a step since the last read overflowed the fixed-point latent hand-off "
-                                       "(a partial outside +-2^17, NaN or inf): its latent values are NaN")
-              : 0;
+    return st ? numeric_fail(st, "a step since the last read") : 0;
 }
 
 int vaeb_synchronize(vaeb_ctx* c) {
