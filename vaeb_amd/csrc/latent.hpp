@@ -610,6 +610,9 @@ DEV void decout_z_body(const StepArgs& a) {
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) b1v[r] = kc4(bb1, 0, 0, kb + 16 * q + 4 * r, 1, H, v1);
+        // W1 / b1 stay ahead of W2 in issue order (hipcc moved some behind the 32 W2 loads):
+        // vmcnt retires in that order, and the hd^T MFMAs and the tanh need only these
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int u = 0; u < 4; ++u)
 #pragma unroll
@@ -637,7 +640,44 @@ DEV void decout_z_body(const StepArgs& a) {
             sv0[u] = bld4(bsl, (partS < npS && ct < nctS) ? (uint32_t)((firstS + (int64_t)ct * nf4S) * 16) : kOOB);
         }
     }
+    // AT: thread (ml, j) of the first 16 Z forms element (ml, j) of the row block's z
+    const int per = 16 * Z;
+    const int l = m0 / a.Mbp;                 // a 16-row block never straddles two planes
+    const int i0 = m0 - l * a.Mbp;
+    const int ml = threadIdx.x / Z, j = threadIdx.x - ml * Z;
+    const int i = i0 + ml;
+    const bool elt = (int)threadIdx.x < per, rv = i < a.Mb;
+    // ZM 2: the element phase's own operands (b4 / b5 of its latent column, the step counter,
+    // the host eps) are loaded behind the slab loads and AHEAD of the weight block: vmcnt
+    // retires in issue order, so the element phase then waits for the slabs and these only and
+    // leaves the weight block in flight (issued behind it, mu / lv waited for all of W1, b1, W2)
+    float b4p = 0.f, b5p = 0.f, epre = 0.f;
+    int64_t stp = 0, grow0p = 0;
+    if constexpr (ZM >= 2) {
+        if (elt) {
+            b4p = a.b4[j];
+            b5p = a.b5[j];
+            if (a.eps_mode == 1 && rv) epre = a.eps_in[((int64_t)l * a.eps_in_ld + i) * Z + j];
+        }
+        stp = a.step ? *a.step : 0;
+        grow0p = (a.order ? (int64_t)ld_launch_const(a.cursor + kCtlNext) * a.row_base_mul : 0) + a.row_base_add;
+    }
     load_block(64 * wave);
+    // the epilogue waves' x / b2 operands.  CT = 2: behind the first block's loads (whose waits
+    // leave them outstanding), long before the epilogue needs them.  CT = 1 issues them at its
+    // first K block: held across the z prologue they spilled under its 128-VGPR cap
+    constexpr bool kPreEarly = CT == 2;
+    if (kPreEarly && wave < 4 * CT) {
+        p.x = x_rows(a);
+        pre = p.prefetch_row(m0, n0 + 16 * (wave >> 2), wave & 3);
+    }
+    // ZM 2: eps as the encoder's reducer draws it (Philox keyed by the global row).  It needs
+    // nothing from the slab sum, so it is drawn while the slabs are in flight
+    float ephil = 0.f;
+    if constexpr (ZM >= 2) {
+        if (elt && rv && a.eps_mode == 0)
+            ephil = philox_normal(a.seed, (uint32_t)(grow0p + i), (uint32_t)(l * Z + j), philox_c23(stp, a.domain));
+    }
     float zb[ZS];
     if constexpr (!AT) {
         const rsrc_t bz = mkbuf(a.z, (int64_t)a.Me * Z * 4);
@@ -650,24 +690,6 @@ DEV void decout_z_body(const StepArgs& a) {
         __shared__ float gs[16][33];
         __shared__ float msum[ZM >= 2 ? 64 : 1][17];   // ZM 2: summed [mu | lv], [column][row]
         __shared__ f32x4 spart[ZM == 2 ? 512 : 1];      // ZM 2: per-partition slab sums
-        const int per = 16 * Z;
-        const int l = m0 / a.Mbp;                 // a 16-row block never straddles two planes
-        const int i0 = m0 - l * a.Mbp;
-        // ZM 2: the element phase's own operands (b4 / b5 of its latent column, the step
-        // counter, the host eps) are loaded BEFORE the slab round trip, so the element phase
-        // after the barrier starts from registers (they were dependent loads behind it)
-        float b4p = 0.f, b5p = 0.f, epre = 0.f;
-        int64_t stp = 0, grow0p = 0;
-        if constexpr (ZM >= 2) {
-            if ((int)threadIdx.x < per) {
-                const int ml = threadIdx.x / Z, j = threadIdx.x - ml * Z;
-                b4p = a.b4[j];
-                b5p = a.b5[j];
-                if (a.eps_mode == 1 && i0 + ml < a.Mb) epre = a.eps_in[((int64_t)l * a.eps_in_ld + i0 + ml) * Z + j];
-            }
-            stp = a.step ? *a.step : 0;
-            grow0p = (a.order ? (int64_t)ld_launch_const(a.cursor + kCtlNext) * a.row_base_mul : 0) + a.row_base_add;
-        }
         if constexpr (ZM == 2) {
             // float4 f (column f >> 2, rows 4 (f & 3) .. + 3) of the row block's nct slabs:
             // partition part = t / nf4 of the 512 threads sums slabs part, part + np, ... in
@@ -700,18 +722,14 @@ DEV void decout_z_body(const StepArgs& a) {
             __syncthreads();
             VAEB_STAMP(a, 6);   // (timeline build) slab sum done
         }
-        if ((int)threadIdx.x < per) {
-            const int ml = threadIdx.x / Z, j = threadIdx.x - ml * Z;
-            const int i = i0 + ml;
-            const bool rv = i < a.Mb;
+        if (elt) {
             float mu, lv, e;
             if constexpr (ZM >= 2) {
                 mu = rv ? msum[j][ml] + b4p : 0.f;
                 lv = rv ? msum[Z + j][ml] + b5p : 0.f;
-                // eps as the encoder's reducer draws it (Philox keyed by the global row)
                 e = 0.f;
                 if (rv) {
-                    if (a.eps_mode == 0) e = philox_normal(a.seed, (uint32_t)(grow0p + i), (uint32_t)(l * Z + j), philox_c23(stp, a.domain));
+                    if (a.eps_mode == 0) e = ephil;
                     else if (a.eps_mode == 1) e = epre;
                 }
                 if (col0) {
@@ -743,30 +761,55 @@ DEV void decout_z_body(const StepArgs& a) {
         }
         __syncthreads();
         VAEB_STAMP(a, 7);   // (timeline build) z formed
+        // (columns 4 t + q <= 31 lie inside zs; those >= Z hold no z and are selected away)
 #pragma unroll
-        for (int t = 0; t < ZS; ++t) zb[t] = (4 * t + q < Z) ? zs[li][4 * t + q] : 0.f;
+        for (int t = 0; t < ZS; ++t) {
+            const float v = zs[li][4 * t + q];
+            zb[t] = (4 * t + q < Z) ? v : 0.f;
+        }
         if (col0 && threadIdx.x < 16 && (a.est == EST_LA || l == 0)) {
             float f = 0.f;
-            for (int j = 0; j < Z; ++j) f += gs[threadIdx.x][j];
-            const int i = i0 + threadIdx.x;
-            float* dst = a.est == EST_LA ? a.la_part + ((int64_t)l * a.Mbp + i) * a.nctZ : a.kl_part + (int64_t)i * a.nctZ;
+            for (int jj = 0; jj < Z; ++jj) f += gs[threadIdx.x][jj];
+            const int ir = i0 + threadIdx.x;
+            float* dst = a.est == EST_LA ? a.la_part + ((int64_t)l * a.Mbp + ir) * a.nctZ : a.kl_part + (int64_t)ir * a.nctZ;
             for (int n = 0; n < a.nctZ; ++n) dst[n] = n == 0 ? f : 0.f;
         }
     }
     for (int kb = 64 * wave; kb < H; kb += 64 * 8) {
         if (kb != 64 * wave) load_block(kb);
-        if (kb == 64 * wave && wave < 4 * CT) {   // epilogue waves, first block: its loads are in flight
+        if (!kPreEarly && kb == 64 * wave && wave < 4 * CT) {   // epilogue waves, first block
             p.x = x_rows(a);
             pre = p.prefetch_row(m0, n0 + 16 * (wave >> 2), wave & 3);
         }
+        // hd^T: the four sub-chunk chains round-robin (each accumulator in its own k order), so
+        // no MFMA waits for the one before it
+        f32x4 t[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) t[u] = zero4();
+#pragma unroll
+        for (int st = 0; st < ZS; ++st)
+#pragma unroll
+            for (int u = 0; u < 4; ++u) t[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1v[st][u], zb[st], t[u], 0, 0, 0);
+        // tanh as a select on the computed value (no exec branch between the MFMAs; a NaN in a
+        // padding row still gives 0); sub-chunk u + 1's tanh is issued under the output MFMAs
+        // of sub-chunk u
         f32x4 hv[4];
+        auto act = [&](int u) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float v = ftanh(t[u][r] + b1v[r][u]);
+                hv[u][r] = rowok ? v : 0.f;
+            }
+        };
+        act(0);
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            f32x4 t = zero4();
+            if (u < 3) act(u + 1);
 #pragma unroll
-            for (int st = 0; st < ZS; ++st) t = __builtin_amdgcn_mfma_f32_16x16x4f32(w1v[st][u], zb[st], t, 0, 0, 0);
+            for (int r = 0; r < 4; ++r)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) hv[u][r] = rowok ? ftanh(t[r] + b1v[r][u]) : 0.f;
+                for (int w = 0; w < NT; ++w)
+                    acc[w] = __builtin_amdgcn_mfma_f32_16x16x4f32(hv[u][r], w2b[u][r][w], acc[w], 0, 0, 0);
         }
         if (col0) {  // hd[m][kb + 16q + 4r + u] for u = 0..3: one float4 per r
             float* dst = a.hd + (int64_t)(m0 + li) * H;
@@ -783,15 +826,8 @@ DEV void decout_z_body(const StepArgs& a) {
                 }
             }
         }
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int w = 0; w < NT; ++w)
-                    acc[w] = __builtin_amdgcn_mfma_f32_16x16x4f32(hv[u][r], w2b[u][r][w], acc[w], 0, 0, 0);
     }
-    if (wave < 4 * CT && 64 * wave >= H) {   // an epilogue wave without a K block (H <= 192)
+    if (!kPreEarly && wave < 4 * CT && 64 * wave >= H) {   // an epilogue wave without a K block (H <= 192)
         p.x = x_rows(a);
         pre = p.prefetch_row(m0, n0 + 16 * (wave >> 2), wave & 3);
     }
