@@ -235,7 +235,14 @@ int vaeb_get_activation(vaeb_ctx* ctx, const char* name, float* out, int64_t n);
  *   Wmu, Wlogs2, bmu, blogs2 (cont); W row-major [in x out].
  * ------------------------------------------------------------------------------------------ */
 #define VAEB_AE_MAX_LAYERS 8
-enum vaeb_ae_otype { VAEB_AE_BINARY = 0, VAEB_AE_CONT = 1 };   /* ae.py:58 / :65 */
+/* VAEB_AE_SE: the vanilla autoencoder's squared-error output (vanilla-ae/ae.py:63-72).  Sigmoid
+ * output Xpr = sigmoid(Hx Wout + bout), theta tail [Wout, bout] as binary, se = sum (X - Xpr)^2 over
+ * the step's rows, objective -se + N(0, s2) prior on theta (+ the latent's own term).
+ * vaeb_ae_train / vaeb_ae_train_many write se / n: a POSITIVE error that falls as training
+ * proceeds, while AdaGrad ascends -se (ae.py:72, 79).  Valid with the POINT latent (-se - 1/2 |Z|^2)
+ * and the ACT latent; with GAUSS it is VAEB_ERR_ARG at create (-se is no log-likelihood, so the ELBO
+ * and the importance-weighted bound have no meaning). */
+enum vaeb_ae_otype { VAEB_AE_BINARY = 0, VAEB_AE_CONT = 1, VAEB_AE_SE = 2 };   /* ae.py:58 / :65 */
 enum vaeb_act      { VAEB_ACT_TANH = 0, VAEB_ACT_SIGMOID = 1, VAEB_ACT_RELU = 2 };   /* f, ae.py:41 */
 /* The latent layer.  POINT: the reference's degenerate VAE above.  GAUSS (extension: a deep VAE
  * on the same layer stack), on the rows X = Xtr[idx], M = |idx|, H the last encoder activation,
@@ -257,8 +264,14 @@ enum vaeb_act      { VAEB_ACT_TANH = 0, VAEB_ACT_SIGMOID = 1, VAEB_ACT_RELU = 2 
  * context's activation buffers, so a step needs K * M <= max_batch: otherwise VAEB_ERR_ARG before
  * the device is touched, with theta, the accumulators and the step unchanged.  A non-finite
  * log w_mk makes the step's value NaN (never dropped).  The evaluation calls behave exactly as on
- * an ELBO context. */
-enum vaeb_ae_latent { VAEB_AE_LATENT_POINT = 0, VAEB_AE_LATENT_GAUSS = 1 };
+ * an ELBO context.
+ *
+ * ACT (the vanilla autoencoder's code, vanilla-ae/ae.py:55): Z = f(H Wz + bz) with the context's
+ * activation f and NO prior on Z; theta layout as POINT; valid with every otype.  vaeb_ae_encode
+ * returns that Z, vaeb_ae_decode is unchanged.  The Gaussian-only calls below are VAEB_ERR_ARG, as
+ * on POINT, and so is iw_samples >= 2.  Its value is 3: latent = 2 is unassigned and stays
+ * VAEB_ERR_ARG at create, as every other unknown value (tests/test_vae_stack_host.py holds 2 to that). */
+enum vaeb_ae_latent { VAEB_AE_LATENT_POINT = 0, VAEB_AE_LATENT_GAUSS = 1, VAEB_AE_LATENT_ACT = 3 };
 
 typedef struct vaeb_ae_config {
     int32_t Dobs;                         /* observation size                                */
@@ -288,7 +301,8 @@ int vaeb_ae_set_params(vaeb_ae* ae, const float* flat, int64_t n);
 int vaeb_ae_get_params(vaeb_ae* ae, float* flat, int64_t n);
 int vaeb_ae_set_adagrad_state(vaeb_ae* ae, const float* flat, int64_t n);
 int vaeb_ae_get_adagrad_state(vaeb_ae* ae, float* flat, int64_t n);
-/* train(idx) (ae.py:82-89): one AdaGrad step on rows Xtr[idx]; writes loglik / n. */
+/* train(idx) (ae.py:82-89): one AdaGrad step on rows Xtr[idx]; writes loglik / n
+ * (VAEB_AE_SE: se / n, positive). */
 int vaeb_ae_train(vaeb_ae* ae, const int32_t* idx, int32_t n, float* out_loglik_per_row);
 /* An epoch of train() calls on consecutive `batch`-sized slices of idx, the last partial
  * slice kept (ae.py:145-151); out[j] = train's value for slice j.  One host sync. */
@@ -296,8 +310,16 @@ int vaeb_ae_train_many(vaeb_ae* ae, const int32_t* idx, int32_t n, int32_t batch
 int vaeb_ae_reconstruct(vaeb_ae* ae, const float* x, int64_t n, float* out);   /* ae.py:92-98  */
 int vaeb_ae_encode(vaeb_ae* ae, const float* x, int64_t n, float* z_out);      /* ae.py:101-107 */
 int vaeb_ae_decode(vaeb_ae* ae, const float* z, int64_t n, float* out);        /* ae.py:110-116 */
+/* Reconstruction error of host x [n x Dobs] on the device, on any context (every otype and latent):
+ *   out_rows[i] = sum_d (x_id - Xpr_id)^2,  Xpr = vaeb_ae_reconstruct(x)
+ * (Gaussian latent: z = mu; cont output: the mean head alone), out_rows may be NULL.  out_sum: the
+ * sum of the row values (double, fixed order), so the vanilla autoencoder's mse()
+ * (vanilla-ae/ae.py:120-121) is out_sum / n.  Runs in max_batch chunks; a row's value does not depend
+ * on max_batch.  Changes no parameter, accumulator, step or pushed eps.  n <= 0 or a NULL x / out_sum
+ * is VAEB_ERR_ARG before the device is touched. */
+int vaeb_ae_sq_error(vaeb_ae* ae, const float* x, int64_t n, double* out_sum, float* out_rows);
 
-/* VAEB_AE_LATENT_GAUSS contexts only (VAEB_ERR_ARG on a point-latent context).  On such a
+/* VAEB_AE_LATENT_GAUSS contexts only (VAEB_ERR_ARG on a POINT or ACT context).  On such a
  * context vaeb_ae_encode returns mu, vaeb_ae_reconstruct decodes z = mu and vaeb_ae_decode is
  * unchanged.
  *

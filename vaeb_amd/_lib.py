@@ -38,15 +38,16 @@ EXPORTS = [
     "vaeb_ae_get_params", "vaeb_ae_set_adagrad_state", "vaeb_ae_get_adagrad_state", "vaeb_ae_train",
     "vaeb_ae_train_many", "vaeb_ae_reconstruct", "vaeb_ae_encode", "vaeb_ae_decode",
     "vaeb_ae_set_eps_mode", "vaeb_ae_push_eps", "vaeb_ae_set_step", "vaeb_ae_get_step", "vaeb_ae_encode_dist",
-    "vaeb_ae_elbo", "vaeb_ae_marginal_ll",
+    "vaeb_ae_elbo", "vaeb_ae_marginal_ll", "vaeb_ae_sq_error",
 ]
 DIAG_EXPORTS = ["vaeb_profile_steps", "vaeb_kernel_name", "vaeb_debug_timeline", "vaeb_test_gemm_bf16",
                 "vaeb_bench_gemm_bf16", "vaeb_graph_status", "vaeb_comm_info", "vaeb_time_update_many", "vaeb_busy",
                 "vaeb_dp_plan", "vaeb_dp_rank_update", "vaeb_get_shadow", "vaeb_dw2_plan"]
 GRAPH_MODES = {0: "off", 1: "not_captured", 2: "replay", 3: "eager_fallback"}
 AE_MAX_LAYERS = 8
-AE_BINARY, AE_CONT = 0, 1
-AE_LATENT = {"point": 0, "gauss": 1}
+AE_BINARY, AE_CONT, AE_SE = 0, 1, 2
+AE_OTYPE = {"binary": AE_BINARY, "cont": AE_CONT, "se": AE_SE}
+AE_LATENT = {"point": 0, "gauss": 1, "act": 3}   # 2 is unassigned
 ACT = {"tanh": 0, "sigmoid": 1, "relu": 2}
 
 
@@ -175,6 +176,7 @@ def load():
         "vaeb_ae_encode_dist": ([_P, _F, _I64, _F, _F, _F], ctypes.c_int),
         "vaeb_ae_elbo": ([_P, _F, _I64, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
         "vaeb_ae_marginal_ll": ([_P, _F, _I64, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), _F], ctypes.c_int),
+        "vaeb_ae_sq_error": ([_P, _F, _I64, ctypes.POINTER(ctypes.c_double), _F], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -546,7 +548,8 @@ class Context:
 class AEContext:
     """One degenerate-vae autoencoder (vaeb_ae_*) on one GPU; latent="gauss": the deep VAE on
     the same layer stack (include/vaeb_hip.h enum vaeb_ae_latent); iw_samples = K >= 2: train on
-    the K-sample importance-weighted bound (K * len(idx) <= max_batch per step)."""
+    the K-sample importance-weighted bound (K * len(idx) <= max_batch per step).  otype="se" with
+    latent="act" is the vanilla squared-error autoencoder (vanilla-ae/ae.py): train returns se / n."""
 
     def __init__(self, Dobs, Denc, Dz, Ddec, otype="binary", act="tanh", s2=1.0, eta=0.01, max_batch=100,
                  device=0, latent="point", iw_samples=1):
@@ -561,12 +564,14 @@ class AEContext:
             c.Denc[i] = int(d)
         for i, d in enumerate(Ddec):
             c.Ddec[i] = int(d)
-        c.otype = {"binary": AE_BINARY, "cont": AE_CONT}[otype]
+        if otype not in AE_OTYPE:
+            raise VaebError(f"otype {otype!r} not supported (binary | cont | se)")
+        c.otype = AE_OTYPE[otype]
         c.act = ACT[act]
         c.s2, c.eta = float(s2), float(eta)
         c.max_batch, c.device = int(max_batch), int(device)
         if latent not in AE_LATENT:
-            raise VaebError(f"latent {latent!r} not supported (point | gauss)")
+            raise VaebError(f"latent {latent!r} not supported (point | gauss | act)")
         c.latent = AE_LATENT[latent]
         c.iw_samples = int(iw_samples)
         self.iw_samples = c.iw_samples
@@ -640,6 +645,15 @@ class AEContext:
 
     def decode(self, z):
         return self._predict(self.lib.vaeb_ae_decode, z, self.Dobs)
+
+    def sq_error(self, x, rows=False):
+        """sum_i sum_d (x_id - reconstruct(x)_id)^2 on the device (vaeb_ae_sq_error, any context);
+        with rows=True also the per-row values: (sum, [n])."""
+        x = np.ascontiguousarray(x, np.float32)
+        out = ctypes.c_double()
+        r = np.empty(x.shape[0], np.float32) if rows else None
+        check(self.lib.vaeb_ae_sq_error(self.h, fptr(x), x.shape[0], ctypes.byref(out), fptr(r) if rows else None))
+        return (out.value, r) if rows else out.value
 
     # ---- Gaussian latent (latent="gauss") ----
     def set_eps_mode(self, mode, seed=0):

@@ -12,6 +12,10 @@ ConstructAE reproduces the reference's theta_0.
 `ConstructVAE` (extension) is the same constructor with a Gaussian latent: mu and log-variance
 heads, z = mu + exp(lv / 2) eps with device Philox noise, and train(idx) returning
 (loglik - KL) / len(idx) (include/vaeb_hip.h enum vaeb_ae_latent).
+
+`ConstructVanillaAE` mirrors the reference's vanilla-ae/ae.py:45-112, the squared-error baseline of
+its report: the code goes through f, Z = f(Hz Wz + bz), there is no prior on Z, the output is
+Xpr = sigmoid(.), logjoint = -se + weight decay, and train(idx) returns se / len(idx).
 """
 from __future__ import annotations
 
@@ -37,20 +41,21 @@ def _values(X):
 
 def param_shapes(Dobs, Denc, Dz, Ddec, otype, latent="point"):
     """theta order of ae.py:51,56,64,72; latent="gauss": [Wz, bz] become
-    [Wzmu, Wzlv, bzmu, bzlv] (the cont output's convention)."""
+    [Wzmu, Wzlv, bzmu, bzlv] (the cont output's convention); latent="act" (the vanilla autoencoder's
+    activated code) has the point layout, otype="se" the binary tail [Wout, bout]."""
     d_in = [Dobs] + list(Denc)
     shp = [(f"W{i}", (d_in[i], d_in[i + 1])) for i in range(len(Denc))]
     shp += [(f"b{i}", (Denc[i],)) for i in range(len(Denc))]
     if latent == "gauss":
         shp += [("Wzmu", (Denc[-1], Dz)), ("Wzlv", (Denc[-1], Dz)), ("bzmu", (Dz,)), ("bzlv", (Dz,))]
-    elif latent == "point":
+    elif latent in ("point", "act"):
         shp += [("Wz", (Denc[-1], Dz)), ("bz", (Dz,))]
     else:
-        raise ValueError(f"latent {latent!r} not supported (point | gauss)")
+        raise ValueError(f"latent {latent!r} not supported (point | gauss | act)")
     d_dec = [Dz] + list(Ddec)
     shp += [(f"W{i}", (d_dec[i], d_dec[i + 1])) for i in range(len(Ddec))]
     shp += [(f"b{i}", (Ddec[i],)) for i in range(len(Ddec))]
-    if otype == "binary":
+    if otype in ("binary", "se"):
         shp += [("Wout", (Ddec[-1], Dobs)), ("bout", (Dobs,))]
     else:
         shp += [("Wmu", (Ddec[-1], Dobs)), ("Wlogs2", (Ddec[-1], Dobs)), ("bmu", (Dobs,)), ("blogs2", (Dobs,))]
@@ -93,8 +98,8 @@ class _AccArena:
 
 
 def _construct(latent, Xtr, Denc, Dz, Ddec, f, s2, inf, otype, max_batch, device, iw_samples=1):
-    """The shared body of ConstructAE / ConstructVAE; returns (ctx, theta)."""
-    if otype not in ("binary", "cont"):
+    """The shared body of ConstructAE / ConstructVAE / ConstructVanillaAE; returns (ctx, theta)."""
+    if otype not in ("binary", "cont") and (latent, otype) != ("act", "se"):
         raise ValueError("otype currently only supports binary.")   # ae.py:74-75 (and cont)
     inf = inf if inf is not None else AdaGrad(0.01)
     Xtr = _values(Xtr)
@@ -154,6 +159,31 @@ def ConstructVAE(Xtr, Denc=(500,), Dz=20, Ddec=(500,), f="tanh", s2=1.0, inf=Non
     train.elbo = lambda X: ctx.elbo(_values(X))
     train.marginal_ll = lambda X, K, rows=False: ctx.marginal_ll(_values(X), K, rows=rows)
     return train, ctx.reconstruct, ctx.encode, ctx.decode, theta
+
+
+def ConstructVanillaAE(Xtr, Denc=(500,), Dz=20, Ddec=(500,), f="tanh", s2=1.0, inf=None, max_batch=None, device=0):
+    """vanilla-ae/ae.py:45-112.  Returns (train, reconstruct, encode, decode, theta): train(idx) takes
+    one AdaGrad step up -se + weight decay on the rows Xtr[idx] and returns se / len(idx) (positive);
+    encode(X) is the activated code f(Hz Wz + bz).  theta_0 is drawn from the global numpy RNG in the
+    order of ConstructAE with a binary output.  train.ctx is the engine context; train.mse(X) is
+    mse(X, reconstruct(X)) computed on the device (vaeb_ae_sq_error), nothing but the sum coming back."""
+    ctx, theta = _construct("act", Xtr, Denc, Dz, Ddec, f, s2, inf, "se", max_batch, device)
+
+    def train(idx):
+        return ctx.train(np.asarray(idx, np.int32))
+
+    def device_mse(X):
+        X = _values(X)
+        return ctx.sq_error(X) / X.shape[0]
+
+    train.ctx = ctx
+    train.mse = device_mse
+    return train, ctx.reconstruct, ctx.encode, ctx.decode, theta
+
+
+def mse(X, Xpr):
+    """vanilla-ae/ae.py:120-121."""
+    return float(np.mean(np.sum((X - Xpr) ** 2, 1)))
 
 
 def rmse(X, Xpr):

@@ -9,8 +9,13 @@
 //                         cont    mu = sigmoid(a_mu), ls2 = a_ls2,
 //                                 loglik += -1/2 (log 2 pi + ls2 + (Y-mu)^2 e^-ls2)
 //                         fused with the output deltas dlogjoint/da     PAeFwd (mode OUT_*)
+//   squared-error output (VAEB_AE_SE, vanilla-ae/ae.py:63-72; vaeb_ae_sq_error on any context):
+//                         P = sigmoid(a), se += (Y - P)^2 (kept positive: the step's value is
+//                         se / M), delta d(-se)/da = 2 (Y - P) P (1 - P)  PAeFwdT<true> (mode OUT_SE)
 //   backward, per layer:  din = (dout W^T) * f'(h)      PAeBwd (mode DACT)
 //                         dZ  = dout W^T - Z            PAeBwd (mode ZPRIOR: N(0,1) prior on Z)
+//   activated latent (VAEB_AE_LATENT_ACT, vanilla-ae/ae.py:55): Z = f(H Wz + bz) through mode ACT,
+//                         dZ = (dout W^T) * f'(Z) through mode DACT with h = Z; no prior on Z
 //   Gaussian latent (VAEB_AE_LATENT_GAUSS; replaces the linear Z layer and its prior):
 //                         mu = H Wzmu + bzmu, lv = H Wzlv + bzlv, z = mu + exp(lv/2) eps,
 //                         -KL partials 1/2 (1 + lv - mu^2 - e^lv)      PAeFwd (mode LATENT, 2 heads)
@@ -32,7 +37,7 @@ namespace vaeb {
 namespace ae {
 
 enum : int { ACT_TANH = 0, ACT_SIGMOID = 1, ACT_RELU = 2 };
-enum : int { F_ACT = 0, F_LINEAR = 1, F_OUT_BIN = 2, F_OUT_CONT = 3, F_LATENT = 4 };
+enum : int { F_ACT = 0, F_LINEAR = 1, F_OUT_BIN = 2, F_OUT_CONT = 3, F_LATENT = 4, F_OUT_SE = 5 };
 enum : int { B_DACT = 0, B_ZPRIOR = 1, B_LATENT = 2, B_LATENT_IW = 3 };
 enum : int { NOISE_ZERO = 0, NOISE_HOST = 1, NOISE_PHILOX = 2 };   // eps of the F_LATENT epilogue
 constexpr float kEpsLog = 1e-7f;   // logpdf.py:86
@@ -57,7 +62,12 @@ DEV float el(rsrc_t b, int ld, int r, int k, int rlim, int klim) {
 }
 
 // ---------------------------------------------------------------- forward layer
-struct PAeFwd {
+// F_OUT_SE (one head): per-(row, 16-column tile) partials of se = sum (Y - P)^2 in llpart, the
+// delta 2 (Y - P) P (1 - P) in dA and P in out; Y with dA == nullptr: the partials only, as the
+// other output modes.  The branch exists only in PAeFwdT<true> (the kernel arguments are the
+// same), so PAeFwd's kernels are what they were without it.
+template <bool SE>
+struct PAeFwdT {
     Dbg a;
     int M, N, K;
     const float* in; int ldin; int in_rows; const int* idx;   // idx: gathered input rows
@@ -136,6 +146,18 @@ struct PAeFwd {
             }
             const int yr = ok ? (yidx ? yidx[m] : m) : 0;
             const float y = ok ? Y[(int64_t)yr * ldy + n] : 0.f;
+            if constexpr (SE) {
+                if (mode == F_OUT_SE) {
+                    const float P = sigmoidf(v), rr = y - P;
+                    if (ok && dA) {
+                        out[(int64_t)m * N + n] = P;
+                        dA[(int64_t)m * N + n] = 2.f * rr * P * (1.f - P);
+                    }
+                    const float s = sum16(ok ? rr * rr : 0.f);
+                    if ((lane & 15) == 0 && m < M) llpart[(int64_t)m * nct + n0 / 16] = s;
+                    continue;
+                }
+            }
             float ll = 0.f;
             if (mode == F_OUT_BIN) {
                 const float P = sigmoidf(v);
@@ -165,6 +187,9 @@ struct PAeFwd {
         }
     }
 };
+
+using PAeFwd = PAeFwdT<false>;
+using PAeFwdSe = PAeFwdT<true>;
 
 // ---------------------------------------------------------------- backward (data) layer
 // din[M x N] = [dout | dout2] [W | W2]^T  (K = K1 or 2 K1), then * f'(h) or - h (Z prior).
@@ -315,6 +340,16 @@ __global__ __launch_bounds__(256) void ae_loglik_kernel(const float* part, int64
         __syncthreads();
     }
     if (threadIdx.x == 0) out[slot] = (float)(sh[0] / (double)M);
+}
+
+// vaeb_ae_sq_error: rows[m] = the row's nct squared-error partials added in ascending tile order
+// (float, one thread per row: the value depends on the row alone, not on the chunk it falls in).
+__global__ __launch_bounds__(256) void ae_row_sum_kernel(const float* part, int M, int nct, float* rows) {
+    const int m = blockIdx.x * 256 + threadIdx.x;
+    if (m >= M) return;
+    float s = 0.f;
+    for (int t = 0; t < nct; ++t) s += part[(int64_t)m * nct + t];
+    rows[m] = s;
 }
 
 // Gaussian latent: the step's value (loglik - KL) / M from the log-lik and the -KL partials,

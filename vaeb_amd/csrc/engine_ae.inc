@@ -20,7 +20,8 @@ struct vaeb_ae {
     int outs_cap = 0;
     // Gaussian latent (c.latent == VAEB_AE_LATENT_GAUSS): a->Z holds z
     float *mu = nullptr, *lv = nullptr, *dmu = nullptr, *dlv = nullptr, *kl = nullptr;
-    double* esum = nullptr;           // vaeb_ae_elbo / vaeb_ae_marginal_ll: one chunk's sum
+    double* esum = nullptr;           // vaeb_ae_elbo / vaeb_ae_marginal_ll / vaeb_ae_sq_error: one chunk's sum
+    float* sq_rows = nullptr;         // vaeb_ae_sq_error: a chunk's row values [max_batch] (first use)
     // vaeb_ae_marginal_ll scratch (allocated on first use): latent terms [max_batch], running
     // (max, sum) [2 max_batch], row values [max_batch]; the observation row of each stacked row
     float* iw = nullptr;
@@ -41,6 +42,7 @@ namespace {
 int ae_alloc(float** p, int64_t n) { return dalloc(p, (size_t)std::max<int64_t>(n, 1)); }
 
 bool ae_gauss(const vaeb_ae* a) { return a->c.latent == VAEB_AE_LATENT_GAUSS; }
+bool ae_act_latent(const vaeb_ae* a) { return a->c.latent == VAEB_AE_LATENT_ACT; }
 bool ae_iw(const vaeb_ae* a) { return a->c.iw_samples >= 2; }
 
 // vaeb_ae_marginal_ll's and the importance-weighted step's scratch, sized by max_batch
@@ -91,8 +93,10 @@ int ae_host_eps_ready(const vaeb_ae* a, int64_t rows) {
 // Forward through the whole network for M rows: in[ri] (ri = idx[m] when idx != null),
 // Y (observations for the loglik / deltas, nullptr for predictions), stop_at_z: encode only.
 // value_only (with train and zin): the output layer leaves the loglik partials and nothing else.
+// sq (with train; vaeb_ae_sq_error): the output layer is the value-only squared error of the mean
+// head, whatever the context's otype.
 int ae_forward(vaeb_ae* a, const float* in, int in_rows, const int* idx, int M, bool train, bool stop_at_z,
-               const float* zin, const AeNoise& nz = AeNoise{}, bool value_only = false) {
+               const float* zin, const AeNoise& nz = AeNoise{}, bool value_only = false, bool sq = false) {
     const vaeb_ae_config& g = a->c;
     hipStream_t s = a->s;
     const int ne = g.n_enc, nd = g.n_dec;
@@ -118,8 +122,8 @@ int ae_forward(vaeb_ae* a, const float* in, int in_rows, const int* idx, int M, 
             p.noise = nz.mode; p.eps_in = nz.eps; p.erow = nz.rows; p.erow0 = nz.row0;
             p.seed = a->seed; p.step = nz.step; p.domain = nz.domain;
             launch_bigk<2>(s, p);
-        } else {
-            p.mode = ae::F_LINEAR; p.out = a->Z;
+        } else {   // Z = H Wz + bz, or f of it (the activated latent)
+            p.mode = ae_act_latent(a) ? ae::F_ACT : ae::F_LINEAR; p.act = g.act; p.out = a->Z;
             launch_bigk<1>(s, p);
         }
         CHECK_LAUNCH();
@@ -134,6 +138,19 @@ int ae_forward(vaeb_ae* a, const float* in, int in_rows, const int* idx, int M, 
         launch_bigk<1>(s, p);
         CHECK_LAUNCH();
     }
+    if (train && (sq || g.otype == VAEB_AE_SE)) {   // squared error: its own instantiation
+        ae::PAeFwdSe p{};
+        p.M = M; p.N = g.Dobs; p.K = a->dd[nd];
+        p.in = a->G[nd]; p.ldin = a->dd[nd]; p.in_rows = M;
+        p.W = a->theta + a->oWo; p.b = a->theta + a->obo;   // cont: the mean head Wmu / bmu alone
+        p.out = a->Xpr;
+        p.Y = in; p.yidx = idx; p.ldy = g.Dobs; p.y_rows = in_rows;
+        p.dA = (sq || value_only) ? nullptr : a->dA; p.llpart = a->ll; p.nct = cdiv(g.Dobs, 16);
+        p.mode = ae::F_OUT_SE;
+        launch_bigk<1>(s, p);
+        CHECK_LAUNCH();
+        return 0;
+    }
     ae::PAeFwd p{};
     p.M = M; p.N = g.Dobs; p.K = a->dd[nd];
     p.in = a->G[nd]; p.ldin = a->dd[nd]; p.in_rows = M;
@@ -141,7 +158,7 @@ int ae_forward(vaeb_ae* a, const float* in, int in_rows, const int* idx, int M, 
     p.out = a->Xpr;
     if (train) { p.Y = in; p.yidx = idx; p.ldy = g.Dobs; p.y_rows = in_rows; }
     p.dA = value_only ? nullptr : a->dA; p.llpart = a->ll; p.nct = cdiv(g.Dobs, 16);
-    if (g.otype == VAEB_AE_BINARY) {
+    if (g.otype != VAEB_AE_CONT) {   // binary, and the predictions (no Y) of a squared-error context
         p.mode = ae::F_OUT_BIN;
         launch_bigk<1>(s, p);
     } else {
@@ -188,6 +205,8 @@ int ae_bwd(vaeb_ae* a, const float* dout, const float* dout2, int K1, const floa
 // train(idx): forward + loglik, then per layer (output first) the data gradient with the
 // old weights followed by the weight update of that layer.  loglik / M -> outs[slot]
 // (Gaussian latent: (loglik - KL) / M, eps from nz; one launch more, the lv head's wgrad).
+// Squared-error output: the partials are se, so outs[slot] = se / M (positive) while the deltas
+// are those of -se.  Activated latent: the decoder's first data gradient is times f'(Z), no - Z.
 int ae_step(vaeb_ae* a, const int* idx, int M, int slot, const AeNoise& nz = AeNoise{}) {
     const vaeb_ae_config& g = a->c;
     const int ne = g.n_enc, nd = g.n_dec, D = g.Dobs;
@@ -212,11 +231,12 @@ int ae_step(vaeb_ae* a, const int* idx, int M, int slot, const AeNoise& nz = AeN
         const float* hin = (i == 0) ? a->Z : a->G[i];
         float* dst = (i == 0) ? a->dZ : a->dG[i];
         if (int rc = ae_bwd(a, a->dG[i + 1], nullptr, a->dd[i + 1], a->theta + a->oWd[i], nullptr, a->dd[i], M, hin,
-                            i == 0 ? (gauss ? ae::B_LATENT : ae::B_ZPRIOR) : ae::B_DACT, dst)) return rc;
+                            i == 0 ? (gauss ? ae::B_LATENT : ae_act_latent(a) ? ae::B_DACT : ae::B_ZPRIOR)
+                                   : ae::B_DACT, dst)) return rc;
         if (int rc = ae_wgrad(a, hin, M, nullptr, a->dd[i], a->dG[i + 1], a->dd[i + 1], M, a->oWd[i], a->obd[i]))
             return rc;
     }
-    // latent layer Z = H W z + bz, or the two heads [mu | lv] = H [Wzmu | Wzlv] + [bzmu | bzlv]
+    // latent layer Z = H W z + bz (dZ: its pre-activation delta on the activated latent), or the two heads [mu | lv] = H [Wzmu | Wzlv] + [bzmu | bzlv]
     if (gauss) {
         if (int rc = ae_bwd(a, a->dmu, a->dlv, g.Dz, a->theta + a->oWz, a->theta + a->oWzl, a->de[ne], M, a->H[ne],
                             ae::B_DACT, a->dH[ne])) return rc;
@@ -366,10 +386,13 @@ int vaeb_ae_create(const vaeb_ae_config* cfg, vaeb_ae** out) {
         return fail(VAEB_ERR_ARG, "bad autoencoder shape");
     for (int i = 0; i < g.n_enc; ++i) if (g.Denc[i] <= 0) return fail(VAEB_ERR_ARG, "Denc[%d] <= 0", i);
     for (int i = 0; i < g.n_dec; ++i) if (g.Ddec[i] <= 0) return fail(VAEB_ERR_ARG, "Ddec[%d] <= 0", i);
-    if (g.otype != VAEB_AE_BINARY && g.otype != VAEB_AE_CONT) return fail(VAEB_ERR_ARG, "otype must be binary|cont");
+    if (g.otype != VAEB_AE_BINARY && g.otype != VAEB_AE_CONT && g.otype != VAEB_AE_SE)
+        return fail(VAEB_ERR_ARG, "otype must be binary|cont|se");
     if (g.act < 0 || g.act > 2) return fail(VAEB_ERR_ARG, "bad activation");
-    if (g.latent != VAEB_AE_LATENT_POINT && g.latent != VAEB_AE_LATENT_GAUSS)
-        return fail(VAEB_ERR_ARG, "latent must be VAEB_AE_LATENT_POINT | VAEB_AE_LATENT_GAUSS (got %d)", g.latent);
+    if (g.latent != VAEB_AE_LATENT_POINT && g.latent != VAEB_AE_LATENT_GAUSS && g.latent != VAEB_AE_LATENT_ACT)
+        return fail(VAEB_ERR_ARG, "latent must be VAEB_AE_LATENT_POINT | _GAUSS | _ACT (got %d)", g.latent);
+    if (g.otype == VAEB_AE_SE && g.latent == VAEB_AE_LATENT_GAUSS)
+        return fail(VAEB_ERR_ARG, "VAEB_AE_SE on a VAEB_AE_LATENT_GAUSS context: -se is no log-likelihood");
     if (!(g.s2 > 0.f) || !(g.eta > 0.f)) return fail(VAEB_ERR_ARG, "s2 and eta must be > 0");
     if (g.iw_samples < 0 || g.iw_samples > (1 << 20))
         return fail(VAEB_ERR_ARG, "iw_samples = %d: 0 to 2^20 (the Philox sample-stream field)", g.iw_samples);
@@ -402,7 +425,7 @@ int vaeb_ae_create(const vaeb_ae_config* cfg, vaeb_ae** out) {
     for (int i = 0; i < g.n_dec; ++i) { a->oWd.push_back(o); o += (int64_t)a->dd[i] * a->dd[i + 1]; }
     for (int i = 0; i < g.n_dec; ++i) { a->obd.push_back(o); o += a->dd[i + 1]; }
     const int64_t HD = (int64_t)a->dd[g.n_dec] * g.Dobs;
-    if (g.otype == VAEB_AE_BINARY) {
+    if (g.otype != VAEB_AE_CONT) {   // binary and se: Wout, bout
         a->oWo = o; o += HD;
         a->obo = o; o += g.Dobs;
     } else {
@@ -461,7 +484,8 @@ int vaeb_ae_destroy(vaeb_ae* a) {
     if (!a) return 0;
     if (a->s) hipStreamSynchronize(a->s);
     std::vector<float*> ps = {a->theta, a->acc, a->data, a->Z, a->dZ, a->Xpr, a->ls2, a->dA, a->dA2, a->ll, a->outs,
-                              a->xin, a->mu, a->lv, a->dmu, a->dlv, a->kl, a->eps_in, a->iw, a->iw_wt, a->iw_val};
+                              a->xin, a->mu, a->lv, a->dmu, a->dlv, a->kl, a->eps_in, a->iw, a->iw_wt, a->iw_val,
+                              a->sq_rows};
     for (auto* v : {&a->H, &a->G, &a->dH, &a->dG}) ps.insert(ps.end(), v->begin(), v->end());
     for (float* p : ps) if (p) hipFree(p);
     if (a->idx) hipFree(a->idx);
@@ -530,6 +554,38 @@ int vaeb_ae_train(vaeb_ae* a, const int32_t* idx, int32_t n, float* out) {
 int vaeb_ae_reconstruct(vaeb_ae* a, const float* x, int64_t n, float* out) { return ae_predict(a, x, n, out, 0); }
 int vaeb_ae_encode(vaeb_ae* a, const float* x, int64_t n, float* z) { return ae_predict(a, x, n, z, 1); }
 int vaeb_ae_decode(vaeb_ae* a, const float* z, int64_t n, float* out) { return ae_predict(a, z, n, out, 2); }
+
+int vaeb_ae_sq_error(vaeb_ae* a, const float* x, int64_t n, double* out_sum, float* out_rows) {
+    if (!a || !x || !out_sum || n <= 0) return fail(VAEB_ERR_ARG, "bad arguments");
+    const vaeb_ae_config& g = a->c;
+    const int nct = cdiv(g.Dobs, 16);
+    if (!a->sq_rows)
+        if (int rc = ae_alloc(&a->sq_rows, g.max_batch)) return rc;
+    if (!a->esum)
+        if (int rc = dalloc(&a->esum, 1)) return rc;
+    double total = 0.0;
+    for (int64_t r0 = 0; r0 < n; r0 += g.max_batch) {
+        const int rows = (int)std::min<int64_t>(g.max_batch, n - r0);
+        HIP_TRY(hipMemcpyAsync(a->xin, x + r0 * g.Dobs, sizeof(float) * (size_t)rows * g.Dobs, hipMemcpyHostToDevice,
+                               a->s));
+        // the deterministic forward (Gaussian latent: z = mu), then the mean head's (Y - P)^2 partials
+        if (int rc = ae_forward(a, a->xin, rows, nullptr, rows, true, false, nullptr, AeNoise{}, true, true)) return rc;
+        hipLaunchKernelGGL(ae::ae_row_sum_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, a->s, a->ll, rows, nct,
+                           a->sq_rows);
+        CHECK_LAUNCH();
+        HIP_TRY(hipMemsetAsync(a->esum, 0, sizeof(double), a->s));
+        hipLaunchKernelGGL(iw_sum_kernel, dim3(1), dim3(256), 0, a->s, a->sq_rows, (int64_t)rows, a->esum);
+        CHECK_LAUNCH();
+        double part = 0.0;
+        HIP_TRY(hipMemcpyAsync(&part, a->esum, sizeof(double), hipMemcpyDeviceToHost, a->s));
+        if (out_rows)
+            HIP_TRY(hipMemcpyAsync(out_rows + r0, a->sq_rows, sizeof(float) * (size_t)rows, hipMemcpyDeviceToHost, a->s));
+        HIP_TRY(hipStreamSynchronize(a->s));
+        total += part;
+    }
+    *out_sum = total;
+    return 0;
+}
 
 // ------------------------------------------------------------------ Gaussian latent
 #define AE_NEED_GAUSS(a, fn)                                                                            \
