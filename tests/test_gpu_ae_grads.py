@@ -10,9 +10,9 @@ also holds the case table and the inputs).  Per parameter block, max|g - g64| / 
 VALUE_RTOL = 2e-5.  tests/test_ae_grads_host.py shows that ten kinds of wrong gradient each miss
 these bounds and that the bounds are all <= 1e-4.  No bound comes from the device.
 
-Order of update.  ae_step updates a layer's weights right after the launch that reads them for the
-data gradient.  A layer updated BEFORE that read would shift the gradient below it by O(eta) = 1e-2
-relative at scaled weights, four orders above the bounds, so the scaled rows cover the order of
+Order of update.  ae_step (in ae_bwd_layer) updates a layer's weights right after the launch that
+reads them for the data gradient.  A layer updated BEFORE that read would shift the gradient below
+it by O(eta) = 1e-2 relative at scaled weights, four orders above the bounds, so the scaled rows cover the order of
 the launches; there is no separate test.
 
 Stale rows.  test_small_batch_after_a_large_one takes a 33-row step, then a 5-row step on the same

@@ -1,5 +1,5 @@
 """The layer-stack engine's training step on the K-sample importance-weighted bound
-(vaeb_ae_config.iw_samples >= 2: vaeb_amd/csrc/engine_ae.inc ae_step_iw, ae_iwae.hpp
+(vaeb_ae_config.iw_samples >= 2: vaeb_amd/csrc/engine_ae.inc ae_step / ae_iw_forward, ae_iwae.hpp
 ae_iw_weight_kernel / ae_iw_plane_sum_kernel, ae_mlp.hpp B_LATENT_IW) against the float64 oracle
 (tests/vae_stack_iwtrain_oracle.py) on identical theta / rows / eps.
 

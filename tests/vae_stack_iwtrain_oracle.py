@@ -1,5 +1,5 @@
 """NumPy oracle of the layer-stack engine's training step on the importance-weighted bound
-(include/vaeb_hip.h vaeb_ae_config.iw_samples, vaeb_amd/csrc/engine_ae.inc ae_step_iw) -- TEST
+(include/vaeb_hip.h vaeb_ae_config.iw_samples, vaeb_amd/csrc/engine_ae.inc ae_step / ae_iw_forward) -- TEST
 HELPER ONLY, on top of tests/vae_stack_oracle.py and tests/vae_stack_iw_oracle.py.
 
 On gathered rows X [M x Dobs] with eps [K, M, Dz], mu and lv once per row:

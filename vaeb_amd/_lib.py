@@ -646,14 +646,18 @@ class AEContext:
     def decode(self, z):
         return self._predict(self.lib.vaeb_ae_decode, z, self.Dobs)
 
-    def sq_error(self, x, rows=False):
-        """sum_i sum_d (x_id - reconstruct(x)_id)^2 on the device (vaeb_ae_sq_error, any context);
-        with rows=True also the per-row values: (sum, [n])."""
+    def _sum_rows(self, fn, x, rows, *args):
+        """fn(h, x, n, *args, &sum, rows or NULL): the sum, with rows=True (sum, per-row values [n])."""
         x = np.ascontiguousarray(x, np.float32)
         out = ctypes.c_double()
         r = np.empty(x.shape[0], np.float32) if rows else None
-        check(self.lib.vaeb_ae_sq_error(self.h, fptr(x), x.shape[0], ctypes.byref(out), fptr(r) if rows else None))
+        check(fn(self.h, fptr(x), x.shape[0], *args, ctypes.byref(out), fptr(r) if rows else None))
         return (out.value, r) if rows else out.value
+
+    def sq_error(self, x, rows=False):
+        """sum_i sum_d (x_id - reconstruct(x)_id)^2 on the device (vaeb_ae_sq_error, any context);
+        with rows=True also the per-row values: (sum, [n])."""
+        return self._sum_rows(self.lib.vaeb_ae_sq_error, x, rows)
 
     # ---- Gaussian latent (latent="gauss") ----
     def set_eps_mode(self, mode, seed=0):
@@ -691,9 +695,4 @@ class AEContext:
     def marginal_ll(self, x, K, rows=False):
         """K-sample importance-weighted estimate of sum_i log p(x_i) (vaeb_ae_marginal_ll); with
         rows=True also the per-row values: (sum, [n])."""
-        x = np.ascontiguousarray(x, np.float32)
-        out = ctypes.c_double()
-        r = np.empty(x.shape[0], np.float32) if rows else None
-        check(self.lib.vaeb_ae_marginal_ll(self.h, fptr(x), x.shape[0], int(K), ctypes.byref(out),
-                                           fptr(r) if rows else None))
-        return (out.value, r) if rows else out.value
+        return self._sum_rows(self.lib.vaeb_ae_marginal_ll, x, rows, int(K))

@@ -98,7 +98,8 @@ class _AccArena:
 
 
 def _construct(latent, Xtr, Denc, Dz, Ddec, f, s2, inf, otype, max_batch, device, iw_samples=1):
-    """The shared body of ConstructAE / ConstructVAE / ConstructVanillaAE; returns (ctx, theta)."""
+    """The shared body of ConstructAE / ConstructVAE / ConstructVanillaAE; returns (train, ctx, theta),
+    train(idx) being one step of the engine on the rows Xtr[idx] with train.ctx = ctx."""
     if otype not in ("binary", "cont") and (latent, otype) != ("act", "se"):
         raise ValueError("otype currently only supports binary.")   # ae.py:74-75 (and cont)
     inf = inf if inf is not None else AdaGrad(0.01)
@@ -120,18 +121,18 @@ def _construct(latent, Xtr, Denc, Dz, Ddec, f, s2, inf, otype, max_batch, device
     arena = _AccArena(ctx)
     updates = inf.construct(arena, theta)
     bind_updates(arena, theta, updates)
-    return ctx, theta
-
-
-def ConstructAE(Xtr, Denc=(500,), Dz=20, Ddec=(500,), f="tanh", s2=1.0, inf=None, otype="binary",
-                max_batch=None, device=0):
-    """ae.py:41-117.  Returns (train, reconstruct, encode, decode, theta)."""
-    ctx, theta = _construct("point", Xtr, Denc, Dz, Ddec, f, s2, inf, otype, max_batch, device)
 
     def train(idx):
         return ctx.train(np.asarray(idx, np.int32))
 
     train.ctx = ctx
+    return train, ctx, theta
+
+
+def ConstructAE(Xtr, Denc=(500,), Dz=20, Ddec=(500,), f="tanh", s2=1.0, inf=None, otype="binary",
+                max_batch=None, device=0):
+    """ae.py:41-117.  Returns (train, reconstruct, encode, decode, theta)."""
+    train, ctx, theta = _construct("point", Xtr, Denc, Dz, Ddec, f, s2, inf, otype, max_batch, device)
     return train, ctx.reconstruct, ctx.encode, ctx.decode, theta
 
 
@@ -148,13 +149,8 @@ def ConstructVAE(Xtr, Denc=(500,), Dz=20, Ddec=(500,), f="tanh", s2=1.0, inf=Non
     marginal_likelihood).  iw_samples = K >= 2: train(idx) steps on the K-sample importance-weighted
     bound instead (K draws per row, sample stream k) and returns that bound / len(idx); a step needs
     K * len(idx) <= max_batch, which defaults to max(100 K, min(4096, N)).  train.iw_samples is K."""
-    ctx, theta = _construct("gauss", Xtr, Denc, Dz, Ddec, f, s2, inf, otype, max_batch, device, iw_samples)
+    train, ctx, theta = _construct("gauss", Xtr, Denc, Dz, Ddec, f, s2, inf, otype, max_batch, device, iw_samples)
     ctx.set_eps_mode(_lib.EPS_PHILOX, seed)
-
-    def train(idx):
-        return ctx.train(np.asarray(idx, np.int32))
-
-    train.ctx = ctx
     train.iw_samples = ctx.iw_samples
     train.elbo = lambda X: ctx.elbo(_values(X))
     train.marginal_ll = lambda X, K, rows=False: ctx.marginal_ll(_values(X), K, rows=rows)
@@ -167,16 +163,12 @@ def ConstructVanillaAE(Xtr, Denc=(500,), Dz=20, Ddec=(500,), f="tanh", s2=1.0, i
     encode(X) is the activated code f(Hz Wz + bz).  theta_0 is drawn from the global numpy RNG in the
     order of ConstructAE with a binary output.  train.ctx is the engine context; train.mse(X) is
     mse(X, reconstruct(X)) computed on the device (vaeb_ae_sq_error), nothing but the sum coming back."""
-    ctx, theta = _construct("act", Xtr, Denc, Dz, Ddec, f, s2, inf, "se", max_batch, device)
-
-    def train(idx):
-        return ctx.train(np.asarray(idx, np.int32))
+    train, ctx, theta = _construct("act", Xtr, Denc, Dz, Ddec, f, s2, inf, "se", max_batch, device)
 
     def device_mse(X):
         X = _values(X)
         return ctx.sq_error(X) / X.shape[0]
 
-    train.ctx = ctx
     train.mse = device_mse
     return train, ctx.reconstruct, ctx.encode, ctx.decode, theta
 

@@ -11,7 +11,7 @@
 //   iw_lse_kernel         iwae.hpp's fold as it stands (plane stride Mbp = R)
 // and iw_sum_kernel adds the chunk's row values in a fixed order.
 //
-// Training on the bound (vaeb_ae_config.iw_samples = K >= 2, engine_ae.inc ae_step_iw) stacks all K
+// Training on the bound (vaeb_ae_config.iw_samples = K >= 2, engine_ae.inc ae_iw_forward) stacks all K
 // planes of the step's M rows in one pass (stacked row g = k * M + m):
 //   ae_iw_sample_kernel      its training form (AeIwArgs.idx set): c0 and yrow from the index
 //                            list, the training domain k << 1

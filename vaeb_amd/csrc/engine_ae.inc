@@ -1,23 +1,46 @@
-// engine_ae.inc -- the degenerate-vae autoencoder (include/vaeb_hip.h vaeb_ae_*) on the
-// fp32 tile engine (ae_mlp.hpp).  Included by vaeb_hip.hip after the VAEB helpers.
+// engine_ae.inc -- the layer-stack engine (include/vaeb_hip.h vaeb_ae_*): the autoencoders and
+// deep VAEs on the fp32 tile engine's kernels (ae_mlp.hpp, ae_iwae.hpp).  Included by
+// vaeb_hip.hip after the VAEB helpers.  Each call and the helper sequence it runs:
+//   vaeb_ae_train(_many)  per batch ae_step: ae_encode | ae_decode_hidden | ae_output(TRAIN) | the value
+//                         (iw_samples >= 2: ae_iw_forward instead), then ae_bwd_decoder | ae_bwd_encoder
+//   vaeb_ae_reconstruct   ae_chunks: ae_encode (zero noise) | ae_decode_hidden | ae_output(PREDICT)
+//   vaeb_ae_encode        ae_chunks: ae_encode (zero noise)
+//   vaeb_ae_decode        ae_chunks: ae_decode_hidden on the caller's z | ae_output(PREDICT)
+//   vaeb_ae_sq_error      ae_chunks: ae_encode (zero noise) | ae_decode_hidden | ae_output(SQ) |
+//                         ae_row_sum_kernel | ae_sum_to_host
+//   vaeb_ae_encode_dist   ae_chunks: ae_encode (evaluation noise when z is wanted)
+//   vaeb_ae_elbo          ae_chunks: ae_encode (evaluation noise) | ae_decode_hidden | ae_output(TRAIN) |
+//                         ae_elbo_kernel | ae_sum_to_host
+//   vaeb_ae_marginal_ll   ae_chunks: ae_encode (zero noise), per pass of sample planes ae_iw_sample_kernel |
+//                         ae_decode_hidden | ae_output(VALUE) | iw_lse_kernel, then ae_sum_to_host
+// vaeb_ae_create lays theta out (an AeLayer per layer and head); device memory is the context's:
+// ae_alloc / ae_grow register it, vaeb_ae_destroy frees the list.
+
+// One affine map of theta: W [K x N] at theta + oW, b [N] at theta + ob.
+struct AeLayer { int K, N; int64_t oW, ob; };
+
+// A layer of one or two heads on the same input (the latent: Wz, or Wzmu and Wzlv; the output:
+// Wout, or Wmu and Wlogs2) with the deltas of the heads' pre-activations.
+struct AeHeads { int n; AeLayer l[2]; float* d[2]; };
 
 struct vaeb_ae {
     vaeb_ae_config c{};
     hipStream_t s = nullptr;
-    std::vector<int> de, dd;          // encoder dims [Dobs, Denc...], decoder dims [Dz, Ddec...]
     int64_t P = 0;
-    std::vector<int64_t> oWe, obe, oWd, obd;
-    int64_t oWz = 0, obz = 0, oWo = 0, obo = 0, oWl = 0, obl = 0;   // out: Wout/bout or Wmu/bmu (+ Wlogs2/blogs2)
-    int64_t oWzl = 0, obzl = 0;       // Gaussian latent: oWz / obz = Wzmu / bzmu, these = Wzlv / bzlv
+    AeLayer enc[VAEB_AE_MAX_LAYERS] = {}, dec[VAEB_AE_MAX_LAYERS] = {};   // Dobs -> Denc..., Dz -> Ddec...
+    AeHeads lat{}, out{};             // d: dZ, or dmu and dlv (Gaussian latent); dA (and dA2, cont)
+    std::vector<void*> owned;         // every device allocation (ae_alloc / ae_grow); freed by vaeb_ae_destroy
     float *theta = nullptr, *acc = nullptr;
     float* data = nullptr;
     int64_t nrows = 0;
     int* idx = nullptr;               // device index list (epoch capacity)
-    int idx_cap = 0;
-    std::vector<float*> H, G, dH, dG; // activations / deltas per layer (H[0], G[0] unused)
+    int64_t idx_cap = 0;
+    // activations / deltas per layer (H[0], G[0] unused)
+    float *H[VAEB_AE_MAX_LAYERS + 1] = {}, *G[VAEB_AE_MAX_LAYERS + 1] = {};
+    float *dH[VAEB_AE_MAX_LAYERS + 1] = {}, *dG[VAEB_AE_MAX_LAYERS + 1] = {};
     float *Z = nullptr, *dZ = nullptr, *Xpr = nullptr, *ls2 = nullptr, *dA = nullptr, *dA2 = nullptr;
     float *ll = nullptr, *outs = nullptr, *xin = nullptr;
-    int outs_cap = 0;
+    int64_t outs_cap = 0;
     // Gaussian latent (c.latent == VAEB_AE_LATENT_GAUSS): a->Z holds z
     float *mu = nullptr, *lv = nullptr, *dmu = nullptr, *dlv = nullptr, *kl = nullptr;
     double* esum = nullptr;           // vaeb_ae_elbo / vaeb_ae_marginal_ll / vaeb_ae_sq_error: one chunk's sum
@@ -39,7 +62,40 @@ struct vaeb_ae {
 
 namespace {
 
-int ae_alloc(float** p, int64_t n) { return dalloc(p, (size_t)std::max<int64_t>(n, 1)); }
+// ------------------------------------------------------------------ device memory
+// n (at least one) zeroed elements, owned by the context from here on.
+template <class T>
+int ae_alloc(vaeb_ae* a, T** p, int64_t n) {
+    const int rc = dalloc(p, (size_t)std::max<int64_t>(n, 1));
+    if (*p) a->owned.push_back(*p);
+    return rc;
+}
+
+// A buffer that exists from its first use on.
+template <class T>
+int ae_lazy(vaeb_ae* a, T** p, int64_t n) { return *p ? 0 : ae_alloc(a, p, n); }
+
+// Replaces *p by a fresh buffer of n elements (contents are not kept).
+template <class T>
+int ae_realloc(vaeb_ae* a, T** p, int64_t n) {
+    auto it = std::find(a->owned.begin(), a->owned.end(), (void*)*p);
+    if (it != a->owned.end()) {
+        hipFree(*p);
+        a->owned.erase(it);
+    }
+    *p = nullptr;
+    return ae_alloc(a, p, n);
+}
+
+// A grow-only buffer: at least n elements.
+template <class T>
+int ae_grow(vaeb_ae* a, T** p, int64_t* cap, int64_t n) {
+    if (n <= *cap) return 0;
+    *cap = 0;
+    if (int rc = ae_realloc(a, p, n)) return rc;
+    *cap = n;
+    return 0;
+}
 
 bool ae_gauss(const vaeb_ae* a) { return a->c.latent == VAEB_AE_LATENT_GAUSS; }
 bool ae_act_latent(const vaeb_ae* a) { return a->c.latent == VAEB_AE_LATENT_ACT; }
@@ -48,40 +104,26 @@ bool ae_iw(const vaeb_ae* a) { return a->c.iw_samples >= 2; }
 // vaeb_ae_marginal_ll's and the importance-weighted step's scratch, sized by max_batch
 int ae_iw_scratch(vaeb_ae* a) {
     const int64_t B = a->c.max_batch;
-    if (!a->iw)
-        if (int rc = ae_alloc(&a->iw, 4 * B)) return rc;
-    if (!a->iw_yrow)
-        if (int rc = dalloc(&a->iw_yrow, (size_t)B)) return rc;
-    return 0;
+    if (int rc = ae_lazy(a, &a->iw, 4 * B)) return rc;
+    return ae_lazy(a, &a->iw_yrow, B);
 }
 
-// eps of one latent forward (ae::PAeFwd F_LATENT): zero (the deterministic predictions),
-// rows of the pushed host eps, or Philox keyed by rows[m] / row0 + m, the step and the domain.
-struct AeNoise {
-    int mode = ae::NOISE_ZERO;
-    const float* eps = nullptr;
-    const int* rows = nullptr;
-    uint32_t row0 = 0;
-    int64_t step = 0;
-    uint32_t domain = 0;
-};
-
-// The noise of rows [r0, r0 + ...) of a call in the context's eps mode: training (domain 0,
-// keyed by the dataset rows idx) or evaluation (domain 1, stream 0, keyed by r0 + m).
-AeNoise ae_noise(const vaeb_ae* a, const int* idx, int64_t r0, int64_t step, bool eval) {
-    AeNoise z;
-    if (a->eps_mode == VAEB_EPS_HOST) {
-        z.mode = ae::NOISE_HOST;
-        z.eps = a->eps_in + r0 * a->c.Dz;
-    } else {
-        z.mode = ae::NOISE_PHILOX;
-        z.rows = idx;
-        z.row0 = (uint32_t)r0;
-        z.step = step;
-        z.domain = eval ? 1u : 0u;
-    }
-    return z;
+int ae_reserve(vaeb_ae* a, int n_idx, int n_out) {
+    if (int rc = ae_grow(a, &a->idx, &a->idx_cap, n_idx)) return rc;
+    return ae_grow(a, &a->outs, &a->outs_cap, n_out);
 }
+
+// ------------------------------------------------------------------ forward
+// Rows of a row-major matrix p [rows x width]: row m of a launch is p[m], or p[idx[m]] when
+// idx is set (the dataset rows of a step; the chunk rows the stacked sample planes observe).
+struct AeRows { const float* p; int rows; const int* idx; };
+
+// eps of one latent forward (ae::PAeFwd F_LATENT): zero (the deterministic predictions), or the
+// noise of rows [r0, r0 + ...) of a call in the context's eps mode: rows of the pushed host eps, or
+// Philox at the step counter, for training (domain 0, keyed by the dataset rows `rows`) or
+// evaluation (domain 1, stream 0, keyed by r0 + m).
+enum AeEps { AE_EPS_ZERO, AE_EPS_TRAIN, AE_EPS_EVAL };
+struct AeNoise { AeEps kind; const int* rows; int64_t r0; };
 
 int ae_host_eps_ready(const vaeb_ae* a, int64_t rows) {
     if (a->eps_mode == VAEB_EPS_HOST && a->eps_rows != rows)
@@ -90,234 +132,222 @@ int ae_host_eps_ready(const vaeb_ae* a, int64_t rows) {
     return 0;
 }
 
-// Forward through the whole network for M rows: in[ri] (ri = idx[m] when idx != null),
-// Y (observations for the loglik / deltas, nullptr for predictions), stop_at_z: encode only.
-// value_only (with train and zin): the output layer leaves the loglik partials and nothing else.
-// sq (with train; vaeb_ae_sq_error): the output layer is the value-only squared error of the mean
-// head, whatever the context's otype.
-int ae_forward(vaeb_ae* a, const float* in, int in_rows, const int* idx, int M, bool train, bool stop_at_z,
-               const float* zin, const AeNoise& nz = AeNoise{}, bool value_only = false, bool sq = false) {
+// The arguments every forward launch of layer l shares: M rows of in through W and b.
+template <class P>
+P ae_fwd_args(const vaeb_ae* a, const AeLayer& l, const AeRows& in, int M) {
+    P p{};
+    p.M = M; p.N = l.N; p.K = l.K;
+    p.in = in.p; p.ldin = l.K; p.in_rows = in.rows; p.idx = in.idx;
+    p.W = a->theta + l.oW; p.b = a->theta + l.ob;
+    return p;
+}
+
+// out = f(in W + b) (ae::F_ACT) or in W + b (ae::F_LINEAR)
+int ae_fwd_layer(vaeb_ae* a, const AeLayer& l, const AeRows& in, int M, int mode, float* out) {
+    ae::PAeFwd p = ae_fwd_args<ae::PAeFwd>(a, l, in, M);
+    p.mode = mode; p.act = a->c.act; p.out = out;
+    launch_bigk<1>(a->s, p);
+    CHECK_LAUNCH();
+    return 0;
+}
+
+// Encoder and latent for the M rows of x: H[], then Z, or with a Gaussian latent mu, lv, the -KL
+// partials kl and Z = mu + exp(lv / 2) eps, eps from nz.
+int ae_encode(vaeb_ae* a, const AeRows& x, int M, const AeNoise& nz) {
+    const int ne = a->c.n_enc;
+    for (int i = 0; i < ne; ++i)
+        if (int rc = ae_fwd_layer(a, a->enc[i], i == 0 ? x : AeRows{a->H[i], M}, M, ae::F_ACT, a->H[i + 1])) return rc;
+    const AeRows h{a->H[ne], M};
+    if (!ae_gauss(a))   // Z = H Wz + bz, or f of it (the activated latent)
+        return ae_fwd_layer(a, a->lat.l[0], h, M, ae_act_latent(a) ? ae::F_ACT : ae::F_LINEAR, a->Z);
+    ae::PAeFwd p = ae_fwd_args<ae::PAeFwd>(a, a->lat.l[0], h, M);
+    p.W2 = a->theta + a->lat.l[1].oW; p.b2 = a->theta + a->lat.l[1].ob;
+    p.mode = ae::F_LATENT; p.out = a->mu; p.out2 = a->lv; p.zout = a->Z;
+    p.llpart = a->kl; p.nct = cdiv(a->c.Dz, 16);
+    p.seed = a->seed;
+    if (nz.kind != AE_EPS_ZERO && a->eps_mode == VAEB_EPS_HOST) {
+        p.noise = ae::NOISE_HOST; p.eps_in = a->eps_in + nz.r0 * a->c.Dz;
+    } else if (nz.kind != AE_EPS_ZERO) {
+        p.noise = ae::NOISE_PHILOX; p.erow = nz.rows; p.erow0 = (uint32_t)nz.r0;
+        p.step = a->step; p.domain = nz.kind == AE_EPS_EVAL ? 1u : 0u;
+    }
+    launch_bigk<2>(a->s, p);
+    CHECK_LAUNCH();
+    return 0;
+}
+
+// The decoder's hidden layers for M rows of z (a->Z or a caller's): G[].
+int ae_decode_hidden(vaeb_ae* a, const float* z, int M) {
+    for (int i = 0; i < a->c.n_dec; ++i)
+        if (int rc = ae_fwd_layer(a, a->dec[i], AeRows{i == 0 ? z : a->G[i], M}, M, ae::F_ACT, a->G[i + 1])) return rc;
+    return 0;
+}
+
+// What the output layer leaves, for M rows of the last decoder activation:
+enum AeOut {
+    AE_OUT_PREDICT,   // the predictions Xpr (+ ls2); no observations
+    AE_OUT_VALUE,     // the per-(row, 16-column tile) partials ll of the context's output value, nothing else
+    AE_OUT_TRAIN,     // the partials, the predictions and the deltas dA (+ dA2)
+    AE_OUT_SQ         // the partials of the mean head's squared error, whatever the context's otype
+};
+
+// y: the observation rows (all but AE_OUT_PREDICT).  The kernel: F_OUT_SE (PAeFwdSe, squared error:
+// its own instantiation; the mean head l[0] alone) for AE_OUT_SQ and for the observed forms of a
+// squared-error context, else by otype F_OUT_CONT (both heads) or F_OUT_BIN (binary, and the
+// predictions of a squared-error context).  A kernel given Y and no dA leaves the partials only.
+int ae_output(vaeb_ae* a, int M, AeOut what, const AeRows& y = AeRows{}) {
     const vaeb_ae_config& g = a->c;
-    hipStream_t s = a->s;
-    const int ne = g.n_enc, nd = g.n_dec;
-    if (!zin) {
-        for (int i = 0; i < ne; ++i) {
-            ae::PAeFwd p{};
-            p.M = M; p.N = a->de[i + 1]; p.K = a->de[i];
-            p.in = (i == 0) ? in : a->H[i]; p.ldin = a->de[i]; p.in_rows = (i == 0) ? in_rows : M;
-            p.idx = (i == 0) ? idx : nullptr;
-            p.W = a->theta + a->oWe[i]; p.b = a->theta + a->obe[i];
-            p.mode = ae::F_ACT; p.act = g.act; p.out = a->H[i + 1];
-            launch_bigk<1>(s, p);
-            CHECK_LAUNCH();
-        }
-        ae::PAeFwd p{};
-        p.M = M; p.N = g.Dz; p.K = a->de[ne];
-        p.in = a->H[ne]; p.ldin = a->de[ne]; p.in_rows = M;
-        p.W = a->theta + a->oWz; p.b = a->theta + a->obz;
-        if (ae_gauss(a)) {
-            p.W2 = a->theta + a->oWzl; p.b2 = a->theta + a->obzl;
-            p.mode = ae::F_LATENT; p.out = a->mu; p.out2 = a->lv; p.zout = a->Z;
-            p.llpart = a->kl; p.nct = cdiv(g.Dz, 16);
-            p.noise = nz.mode; p.eps_in = nz.eps; p.erow = nz.rows; p.erow0 = nz.row0;
-            p.seed = a->seed; p.step = nz.step; p.domain = nz.domain;
-            launch_bigk<2>(s, p);
-        } else {   // Z = H Wz + bz, or f of it (the activated latent)
-            p.mode = ae_act_latent(a) ? ae::F_ACT : ae::F_LINEAR; p.act = g.act; p.out = a->Z;
-            launch_bigk<1>(s, p);
-        }
-        CHECK_LAUNCH();
-        if (stop_at_z) return 0;
-    }
-    for (int i = 0; i < nd; ++i) {
-        ae::PAeFwd p{};
-        p.M = M; p.N = a->dd[i + 1]; p.K = a->dd[i];
-        p.in = (i == 0) ? (zin ? zin : a->Z) : a->G[i]; p.ldin = a->dd[i]; p.in_rows = M;
-        p.W = a->theta + a->oWd[i]; p.b = a->theta + a->obd[i];
-        p.mode = ae::F_ACT; p.act = g.act; p.out = a->G[i + 1];
-        launch_bigk<1>(s, p);
-        CHECK_LAUNCH();
-    }
-    if (train && (sq || g.otype == VAEB_AE_SE)) {   // squared error: its own instantiation
-        ae::PAeFwdSe p{};
-        p.M = M; p.N = g.Dobs; p.K = a->dd[nd];
-        p.in = a->G[nd]; p.ldin = a->dd[nd]; p.in_rows = M;
-        p.W = a->theta + a->oWo; p.b = a->theta + a->obo;   // cont: the mean head Wmu / bmu alone
+    const bool obs = what != AE_OUT_PREDICT, deltas = what == AE_OUT_PREDICT || what == AE_OUT_TRAIN;
+    const bool se = what == AE_OUT_SQ || (obs && g.otype == VAEB_AE_SE), cont = g.otype == VAEB_AE_CONT;
+    auto args = [&](auto p, int mode) {
+        p = ae_fwd_args<decltype(p)>(a, a->out.l[0], AeRows{a->G[g.n_dec], M}, M);
         p.out = a->Xpr;
-        p.Y = in; p.yidx = idx; p.ldy = g.Dobs; p.y_rows = in_rows;
-        p.dA = (sq || value_only) ? nullptr : a->dA; p.llpart = a->ll; p.nct = cdiv(g.Dobs, 16);
-        p.mode = ae::F_OUT_SE;
-        launch_bigk<1>(s, p);
-        CHECK_LAUNCH();
-        return 0;
-    }
-    ae::PAeFwd p{};
-    p.M = M; p.N = g.Dobs; p.K = a->dd[nd];
-    p.in = a->G[nd]; p.ldin = a->dd[nd]; p.in_rows = M;
-    p.W = a->theta + a->oWo; p.b = a->theta + a->obo;
-    p.out = a->Xpr;
-    if (train) { p.Y = in; p.yidx = idx; p.ldy = g.Dobs; p.y_rows = in_rows; }
-    p.dA = value_only ? nullptr : a->dA; p.llpart = a->ll; p.nct = cdiv(g.Dobs, 16);
-    if (g.otype != VAEB_AE_CONT) {   // binary, and the predictions (no Y) of a squared-error context
-        p.mode = ae::F_OUT_BIN;
-        launch_bigk<1>(s, p);
+        if (obs) { p.Y = y.p; p.yidx = y.idx; p.ldy = g.Dobs; p.y_rows = y.rows; }
+        p.dA = deltas ? a->dA : nullptr; p.llpart = a->ll; p.nct = cdiv(g.Dobs, 16);
+        p.mode = mode;
+        return p;
+    };
+    if (se) {
+        launch_bigk<1>(a->s, args(ae::PAeFwdSe{}, ae::F_OUT_SE));
+    } else if (!cont) {
+        launch_bigk<1>(a->s, args(ae::PAeFwd{}, ae::F_OUT_BIN));
     } else {
-        p.mode = ae::F_OUT_CONT;
-        p.W2 = a->theta + a->oWl; p.b2 = a->theta + a->obl; p.out2 = a->ls2;
-        p.dA2 = value_only ? nullptr : a->dA2;
-        launch_bigk<2>(s, p);
+        ae::PAeFwd p = args(ae::PAeFwd{}, ae::F_OUT_CONT);
+        p.W2 = a->theta + a->out.l[1].oW; p.b2 = a->theta + a->out.l[1].ob; p.out2 = a->ls2;
+        p.dA2 = deltas ? a->dA2 : nullptr;
+        launch_bigk<2>(a->s, p);
     }
     CHECK_LAUNCH();
     return 0;
 }
 
-// One weight-gradient + AdaGrad launch for W [Kin x N] / b [N] from in (gathered through
-// idx for the first layer) and the layer's output delta.
-int ae_wgrad(vaeb_ae* a, const float* in, int in_rows, const int* idx, int Kin, const float* dout, int N, int M,
-             int64_t offW, int64_t offb) {
+// ------------------------------------------------------------------ backward
+// One weight-gradient + AdaGrad launch for layer l from its input in (gathered through
+// in.idx for the first layer) and its output delta over M rows.
+int ae_wgrad(vaeb_ae* a, const AeLayer& l, const AeRows& in, const float* dout, int M) {
     ae::PAeWgrad p{};
-    p.M = Kin + 1; p.N = N; p.K = M;
-    p.in = in; p.ldin = Kin; p.in_rows = in_rows; p.idx = idx; p.Kin = Kin;
+    p.M = l.K + 1; p.N = l.N; p.K = M;
+    p.in = in.p; p.ldin = l.K; p.in_rows = in.rows; p.idx = in.idx; p.Kin = l.K;
     p.dout = dout;
-    p.theta = a->theta; p.accum = a->acc; p.offW = offW; p.offb = offb;
+    p.theta = a->theta; p.accum = a->acc; p.offW = l.oW; p.offb = l.ob;
     p.eta = a->c.eta; p.inv_s2 = 1.0f / a->c.s2;
     launch_bigk<1>(a->s, p);
     CHECK_LAUNCH();
     return 0;
 }
 
+// Backward through one layer of nh (1 or 2) heads l[] with the pre-activation deltas d[] on the
+// input `in` over M rows: the data gradient [d0 | d1] [W0 | W1]^T, then mode, into din with the
+// old weights (din == nullptr: none, no data gradient into x), followed by each head's update.
+// This order is load-bearing (ae_mlp.hpp: every weight is updated only after the last kernel of
+// the step that reads it), and it exists here only.
 template <bool IW = false>
-int ae_bwd(vaeb_ae* a, const float* dout, const float* dout2, int K1, const float* W, const float* W2, int N, int M,
-           const float* h, int mode, float* din) {
-    ae::PAeBwdT<IW> p{};
-    p.M = M; p.N = N; p.K = dout2 ? 2 * K1 : K1;
-    p.dout = dout; p.dout2 = dout2; p.K1 = K1; p.W = W; p.W2 = W2;
-    p.h = h; p.mode = mode; p.act = a->c.act; p.din = din;
-    if (mode == ae::B_LATENT || mode == ae::B_LATENT_IW) {
-        p.h = a->mu; p.h2 = a->lv; p.h3 = a->Z; p.din = a->dmu; p.din2 = a->dlv;
+int ae_bwd_layer(vaeb_ae* a, const AeLayer* l, float* const* d, int nh, const AeRows& in, int M, int mode, float* din) {
+    if (din) {
+        ae::PAeBwdT<IW> p{};
+        p.M = M; p.N = l[0].K; p.K = nh * l[0].N;
+        p.dout = d[0]; p.K1 = l[0].N; p.W = a->theta + l[0].oW;
+        if (nh == 2) { p.dout2 = d[1]; p.W2 = a->theta + l[1].oW; }
+        p.h = in.p; p.mode = mode; p.act = a->c.act; p.din = din;
+        if (mode == ae::B_LATENT || mode == ae::B_LATENT_IW) {
+            p.h = a->mu; p.h2 = a->lv; p.h3 = a->Z; p.din = a->dmu; p.din2 = a->dlv;
+        }
+        if constexpr (IW) { p.wt = a->iw_wt; p.Mp = M / a->c.iw_samples; }
+        launch_bigk<1>(a->s, p);
+        CHECK_LAUNCH();
     }
-    if constexpr (IW) { p.wt = a->iw_wt; p.Mp = M / a->c.iw_samples; }
-    launch_bigk<1>(a->s, p);
-    CHECK_LAUNCH();
+    for (int j = 0; j < nh; ++j)
+        if (int rc = ae_wgrad(a, l[j], in, d[j], M)) return rc;
     return 0;
 }
 
-// train(idx): forward + loglik, then per layer (output first) the data gradient with the
-// old weights followed by the weight update of that layer.  loglik / M -> outs[slot]
-// (Gaussian latent: (loglik - KL) / M, eps from nz; one launch more, the lv head's wgrad).
-// Squared-error output: the partials are se, so outs[slot] = se / M (positive) while the deltas
-// are those of -se.  Activated latent: the decoder's first data gradient is times f'(Z), no - Z.
-int ae_step(vaeb_ae* a, const int* idx, int M, int slot, const AeNoise& nz = AeNoise{}) {
-    const vaeb_ae_config& g = a->c;
-    const int ne = g.n_enc, nd = g.n_dec, D = g.Dobs;
-    const bool cont = g.otype == VAEB_AE_CONT, gauss = ae_gauss(a);
-    if (int rc = ae_forward(a, a->data, (int)a->nrows, idx, M, true, false, nullptr, nz)) return rc;
-    if (gauss)
-        hipLaunchKernelGGL(ae::ae_elbo_kernel, dim3(1), dim3(256), 0, a->s, a->ll, (int64_t)M * cdiv(D, 16), a->kl,
-                           (int64_t)M * cdiv(g.Dz, 16), M, a->outs, slot, (double*)nullptr);
-    else
-        hipLaunchKernelGGL(ae::ae_loglik_kernel, dim3(1), dim3(256), 0, a->s, a->ll, (int64_t)M * cdiv(D, 16), M,
-                           a->outs, slot);
-    CHECK_LAUNCH();
-    // output layer
-    const int Hd = a->dd[nd];
-    if (int rc = ae_bwd(a, a->dA, cont ? a->dA2 : nullptr, D, a->theta + a->oWo, cont ? a->theta + a->oWl : nullptr,
-                        Hd, M, a->G[nd], ae::B_DACT, a->dG[nd])) return rc;
-    if (int rc = ae_wgrad(a, a->G[nd], M, nullptr, Hd, a->dA, D, M, a->oWo, a->obo)) return rc;
-    if (cont)
-        if (int rc = ae_wgrad(a, a->G[nd], M, nullptr, Hd, a->dA2, D, M, a->oWl, a->obl)) return rc;
-    // decoder layers (top down): dG[i+1] is the pre-activation delta of layer i
-    for (int i = nd - 1; i >= 0; --i) {
-        const float* hin = (i == 0) ? a->Z : a->G[i];
-        float* dst = (i == 0) ? a->dZ : a->dG[i];
-        if (int rc = ae_bwd(a, a->dG[i + 1], nullptr, a->dd[i + 1], a->theta + a->oWd[i], nullptr, a->dd[i], M, hin,
-                            i == 0 ? (gauss ? ae::B_LATENT : ae_act_latent(a) ? ae::B_DACT : ae::B_ZPRIOR)
-                                   : ae::B_DACT, dst)) return rc;
-        if (int rc = ae_wgrad(a, hin, M, nullptr, a->dd[i], a->dG[i + 1], a->dd[i + 1], M, a->oWd[i], a->obd[i]))
-            return rc;
-    }
-    // latent layer Z = H W z + bz (dZ: its pre-activation delta on the activated latent), or the two heads [mu | lv] = H [Wzmu | Wzlv] + [bzmu | bzlv]
-    if (gauss) {
-        if (int rc = ae_bwd(a, a->dmu, a->dlv, g.Dz, a->theta + a->oWz, a->theta + a->oWzl, a->de[ne], M, a->H[ne],
-                            ae::B_DACT, a->dH[ne])) return rc;
-        if (int rc = ae_wgrad(a, a->H[ne], M, nullptr, a->de[ne], a->dmu, g.Dz, M, a->oWz, a->obz)) return rc;
-        if (int rc = ae_wgrad(a, a->H[ne], M, nullptr, a->de[ne], a->dlv, g.Dz, M, a->oWzl, a->obzl)) return rc;
-    } else {
-        if (int rc = ae_bwd(a, a->dZ, nullptr, g.Dz, a->theta + a->oWz, nullptr, a->de[ne], M, a->H[ne], ae::B_DACT,
-                            a->dH[ne])) return rc;
-        if (int rc = ae_wgrad(a, a->H[ne], M, nullptr, a->de[ne], a->dZ, g.Dz, M, a->oWz, a->obz)) return rc;
-    }
-    // encoder layers (top down); no data gradient into X
-    for (int i = ne - 1; i >= 0; --i) {
-        if (i > 0)
-            if (int rc = ae_bwd(a, a->dH[i + 1], nullptr, a->de[i + 1], a->theta + a->oWe[i], nullptr, a->de[i], M,
-                                a->H[i], ae::B_DACT, a->dH[i])) return rc;
-        const float* in = (i == 0) ? a->data : a->H[i];
-        if (int rc = ae_wgrad(a, in, i == 0 ? (int)a->nrows : M, i == 0 ? idx : nullptr, a->de[i], a->dH[i + 1],
-                              a->de[i + 1], M, a->oWe[i], a->obe[i])) return rc;
-    }
-    return 0;
+// Output layer and decoder (top down) over R rows; dG[i+1] is the pre-activation delta of layer i.
+// mode0 is the first decoder layer's: B_ZPRIOR (dZ = dz - Z), B_DACT (the activated latent: times
+// f'(Z), no - Z), B_LATENT (dmu, dlv) or B_LATENT_IW (dmu_k, dlv_k per stacked row).
+int ae_bwd_decoder(vaeb_ae* a, int R, int mode0) {
+    const int nd = a->c.n_dec, act = ae::B_DACT;
+    if (int rc = ae_bwd_layer(a, a->out.l, a->out.d, a->out.n, AeRows{a->G[nd], R}, R, act, a->dG[nd])) return rc;
+    for (int i = nd - 1; i > 0; --i)
+        if (int rc = ae_bwd_layer(a, &a->dec[i], &a->dG[i + 1], 1, AeRows{a->G[i], R}, R, act, a->dG[i])) return rc;
+    const AeRows z{a->Z, R};
+    return mode0 == ae::B_LATENT_IW ? ae_bwd_layer<true>(a, a->dec, &a->dG[1], 1, z, R, mode0, a->dZ)
+                                    : ae_bwd_layer(a, a->dec, &a->dG[1], 1, z, R, mode0, a->dZ);
 }
 
-// train(idx) on the K-sample importance-weighted bound (c.iw_samples = K >= 2, ae_iwae.hpp): the
-// encoder once on the M rows, the decoder forward and backward on the K * M stacked rows
-// (g = k * M + m) with the output deltas scaled by the normalised weights, the K planes of
-// dmu / dlv summed, then the encoder's backward on M rows as in ae_step.  L_K / M -> outs[slot].
+// The latent layer Z = H Wz + bz (dZ: its pre-activation delta on the activated latent), or the
+// two heads [mu | lv] = H [Wzmu | Wzlv] + [bzmu | bzlv], then the encoder (top down) over the M
+// rows of x.
+int ae_bwd_encoder(vaeb_ae* a, const AeRows& x, int M) {
+    const int ne = a->c.n_enc, act = ae::B_DACT;
+    if (int rc = ae_bwd_layer(a, a->lat.l, a->lat.d, a->lat.n, AeRows{a->H[ne], M}, M, act, a->dH[ne])) return rc;
+    for (int i = ne - 1; i > 0; --i)
+        if (int rc = ae_bwd_layer(a, &a->enc[i], &a->dH[i + 1], 1, AeRows{a->H[i], M}, M, act, a->dH[i])) return rc;
+    return ae_bwd_layer(a, a->enc, &a->dH[1], 1, x, M, act, nullptr);
+}
+
+// The forward of a step on the K-sample importance-weighted bound (c.iw_samples = K >= 2,
+// ae_iwae.hpp): the encoder once on the M rows, the decoder on the K * M stacked rows
+// (g = k * M + m) with the output deltas scaled by the normalised weights.  L_K / M -> outs[slot].
 // lb: the step's offset in the call's idx list of n rows (host eps: sample k of list position i
 // at row k * n + i).
-int ae_step_iw(vaeb_ae* a, const int* idx, int M, int slot, int64_t lb, int64_t n, int64_t step) {
+int ae_iw_forward(vaeb_ae* a, const AeRows& x, int M, int slot, int64_t lb, int64_t n) {
     const vaeb_ae_config& g = a->c;
-    const int ne = g.n_enc, nd = g.n_dec, D = g.Dobs, K = g.iw_samples, KM = K * M;
-    const bool cont = g.otype == VAEB_AE_CONT;
-    if (int rc = ae_forward(a, a->data, (int)a->nrows, idx, M, false, true, nullptr)) return rc;   // mu, lv
+    const int D = g.Dobs, K = g.iw_samples, KM = K * M;
+    if (int rc = ae_encode(a, x, M, AeNoise{})) return rc;   // mu, lv
     ae::AeIwArgs q{};
     q.Dz = g.Dz; q.R = M; q.S = K; q.k0 = 0; q.row0 = lb; q.n = n;
     q.eps_mode = a->eps_mode == VAEB_EPS_HOST ? 1 : 0;
-    q.seed = a->seed; q.step = step; q.eps_in = a->eps_in;
-    q.mu = a->mu; q.lv = a->lv; q.z = a->Z; q.lat = a->iw; q.yrow = a->iw_yrow; q.idx = idx;
+    q.seed = a->seed; q.step = a->step; q.eps_in = a->eps_in;
+    q.mu = a->mu; q.lv = a->lv; q.z = a->Z; q.lat = a->iw; q.yrow = a->iw_yrow; q.idx = x.idx;
     hipLaunchKernelGGL(ae::ae_iw_sample_kernel, dim3(cdiv(KM, 16)), dim3(256), 0, a->s, q);
     CHECK_LAUNCH();
-    if (int rc = ae_forward(a, a->data, (int)a->nrows, a->iw_yrow, KM, true, false, a->Z)) return rc;
+    if (int rc = ae_decode_hidden(a, a->Z, KM)) return rc;
+    if (int rc = ae_output(a, KM, AE_OUT_TRAIN, AeRows{x.p, x.rows, a->iw_yrow})) return rc;
     ae::AeIwWeightArgs w{};
     w.M = M; w.K = K; w.D = D; w.nct = cdiv(D, 16); w.logK = std::log((double)K);
     w.llpart = a->ll; w.lat = a->iw; w.lw = a->iw_lw; w.wt = a->iw_wt; w.rowval = a->iw_val;
-    w.dA = a->dA; w.dA2 = cont ? a->dA2 : nullptr;
+    w.dA = a->dA; w.dA2 = g.otype == VAEB_AE_CONT ? a->dA2 : nullptr;
     hipLaunchKernelGGL(ae::ae_iw_weight_kernel, dim3(M), dim3(256), 0, a->s, w);
     CHECK_LAUNCH();
     hipLaunchKernelGGL(ae::ae_loglik_kernel, dim3(1), dim3(256), 0, a->s, a->iw_val, (int64_t)M, M, a->outs, slot);
     CHECK_LAUNCH();
-    // output layer and decoder on the stacked rows
-    const int Hd = a->dd[nd];
-    if (int rc = ae_bwd(a, a->dA, cont ? a->dA2 : nullptr, D, a->theta + a->oWo, cont ? a->theta + a->oWl : nullptr,
-                        Hd, KM, a->G[nd], ae::B_DACT, a->dG[nd])) return rc;
-    if (int rc = ae_wgrad(a, a->G[nd], KM, nullptr, Hd, a->dA, D, KM, a->oWo, a->obo)) return rc;
-    if (cont)
-        if (int rc = ae_wgrad(a, a->G[nd], KM, nullptr, Hd, a->dA2, D, KM, a->oWl, a->obl)) return rc;
-    for (int i = nd - 1; i >= 0; --i) {
-        const float* hin = (i == 0) ? a->Z : a->G[i];
-        if (int rc = i == 0 ? ae_bwd<true>(a, a->dG[1], nullptr, a->dd[1], a->theta + a->oWd[0], nullptr, a->dd[0], KM,
-                                           hin, ae::B_LATENT_IW, nullptr)
-                            : ae_bwd(a, a->dG[i + 1], nullptr, a->dd[i + 1], a->theta + a->oWd[i], nullptr, a->dd[i], KM,
-                                     hin, ae::B_DACT, a->dG[i])) return rc;
-        if (int rc = ae_wgrad(a, hin, KM, nullptr, a->dd[i], a->dG[i + 1], a->dd[i + 1], KM, a->oWd[i], a->obd[i]))
-            return rc;
+    return 0;
+}
+
+// train(idx) on the M dataset rows idx (the slice at offset lb of the call's list of n rows):
+// forward + value, then the backward.  loglik / M -> outs[slot]; Gaussian latent: (loglik - KL) / M,
+// eps drawn at the step counter, which then advances (the one place; point contexts have none).
+// Squared-error output: the partials are se, so outs[slot] = se / M (positive) while the deltas
+// are those of -se.  iw_samples >= 2: ae_iw_forward, the decoder's backward on the K * M stacked
+// rows, the K planes of dmu / dlv summed, then the encoder's backward on M rows as ever.
+int ae_step(vaeb_ae* a, const int* idx, int M, int slot, int64_t lb, int64_t n) {
+    const vaeb_ae_config& g = a->c;
+    const bool gauss = ae_gauss(a), iw = ae_iw(a);
+    const AeRows x{a->data, (int)a->nrows, idx};
+    const int R = iw ? g.iw_samples * M : M;
+    if (iw) {
+        if (int rc = ae_iw_forward(a, x, M, slot, lb, n)) return rc;
+    } else {
+        if (int rc = ae_encode(a, x, M, AeNoise{AE_EPS_TRAIN, idx, lb})) return rc;
+        if (int rc = ae_decode_hidden(a, a->Z, M)) return rc;
+        if (int rc = ae_output(a, M, AE_OUT_TRAIN, x)) return rc;
+        if (gauss)
+            hipLaunchKernelGGL(ae::ae_elbo_kernel, dim3(1), dim3(256), 0, a->s, a->ll, (int64_t)M * cdiv(g.Dobs, 16),
+                               a->kl, (int64_t)M * cdiv(g.Dz, 16), M, a->outs, slot, (double*)nullptr);
+        else
+            hipLaunchKernelGGL(ae::ae_loglik_kernel, dim3(1), dim3(256), 0, a->s, a->ll, (int64_t)M * cdiv(g.Dobs, 16),
+                               M, a->outs, slot);
+        CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(ae::ae_iw_plane_sum_kernel, dim3(cdiv(M * g.Dz, 256)), dim3(256), 0, a->s, a->dmu, a->dlv, M,
-                       g.Dz, K);
-    CHECK_LAUNCH();
-    // the two heads and the encoder on the M rows, as ae_step
-    if (int rc = ae_bwd(a, a->dmu, a->dlv, g.Dz, a->theta + a->oWz, a->theta + a->oWzl, a->de[ne], M, a->H[ne],
-                        ae::B_DACT, a->dH[ne])) return rc;
-    if (int rc = ae_wgrad(a, a->H[ne], M, nullptr, a->de[ne], a->dmu, g.Dz, M, a->oWz, a->obz)) return rc;
-    if (int rc = ae_wgrad(a, a->H[ne], M, nullptr, a->de[ne], a->dlv, g.Dz, M, a->oWzl, a->obzl)) return rc;
-    for (int i = ne - 1; i >= 0; --i) {
-        if (i > 0)
-            if (int rc = ae_bwd(a, a->dH[i + 1], nullptr, a->de[i + 1], a->theta + a->oWe[i], nullptr, a->de[i], M,
-                                a->H[i], ae::B_DACT, a->dH[i])) return rc;
-        const float* in = (i == 0) ? a->data : a->H[i];
-        if (int rc = ae_wgrad(a, in, i == 0 ? (int)a->nrows : M, i == 0 ? idx : nullptr, a->de[i], a->dH[i + 1],
-                              a->de[i + 1], M, a->oWe[i], a->obe[i])) return rc;
+    if (int rc = ae_bwd_decoder(a, R, iw ? ae::B_LATENT_IW : gauss ? ae::B_LATENT
+                                         : ae_act_latent(a) ? ae::B_DACT : ae::B_ZPRIOR)) return rc;
+    if (iw) {
+        hipLaunchKernelGGL(ae::ae_iw_plane_sum_kernel, dim3(cdiv(M * g.Dz, 256)), dim3(256), 0, a->s, a->dmu, a->dlv,
+                           M, g.Dz, g.iw_samples);
+        CHECK_LAUNCH();
     }
+    if (int rc = ae_bwd_encoder(a, x, M)) return rc;
+    if (gauss) ++a->step;
     return 0;
 }
 
@@ -329,40 +359,58 @@ int ae_check_idx(vaeb_ae* a, const int32_t* idx, int32_t n) {
     return 0;
 }
 
-int ae_reserve(vaeb_ae* a, int n_idx, int n_out) {
-    if (n_idx > a->idx_cap) {
-        if (a->idx) hipFree(a->idx);
-        a->idx = nullptr;
-        if (int rc = dalloc(&a->idx, (size_t)n_idx)) return rc;
-        a->idx_cap = n_idx;
-    }
-    if (n_out > a->outs_cap) {
-        if (a->outs) hipFree(a->outs);
-        a->outs = nullptr;
-        if (int rc = dalloc(&a->outs, (size_t)n_out)) return rc;
-        a->outs_cap = n_out;
+// ------------------------------------------------------------------ calls over host rows
+// Walks the n rows of the host matrix x [n x width] in chunks of at most max_batch rows: uploads
+// a chunk to xin, then body(r0, rows).  The body ends in the chunk's one stream synchronise.
+template <class Body>
+int ae_chunks(vaeb_ae* a, const float* x, int64_t n, int width, Body body) {
+    const int64_t B = a->c.max_batch;
+    for (int64_t r0 = 0; r0 < n; r0 += B) {
+        const int rows = (int)std::min<int64_t>(B, n - r0);
+        HIP_TRY(hipMemcpyAsync(a->xin, x + r0 * width, sizeof(float) * (size_t)rows * width, hipMemcpyHostToDevice,
+                               a->s));
+        if (int rc = body(r0, rows)) return rc;
     }
     return 0;
 }
 
-// reconstruct / encode / decode over host rows in max_batch chunks.
-int ae_predict(vaeb_ae* a, const float* x, int64_t n, float* out, int what) {
+// The fixed-order fp64 sum of the chunk's row values v [rows] -> esum (v == nullptr: a kernel of
+// the body has written esum already), added to *total on the host; the rows themselves to
+// out_rows when that is set.  Ends in the chunk's one stream synchronise.
+int ae_sum_to_host(vaeb_ae* a, const float* v, int rows, double* total, float* out_rows = nullptr) {
+    if (v) {
+        HIP_TRY(hipMemsetAsync(a->esum, 0, sizeof(double), a->s));
+        hipLaunchKernelGGL(iw_sum_kernel, dim3(1), dim3(256), 0, a->s, v, (int64_t)rows, a->esum);
+        CHECK_LAUNCH();
+    }
+    double part = 0.0;
+    HIP_TRY(hipMemcpyAsync(&part, a->esum, sizeof(double), hipMemcpyDeviceToHost, a->s));
+    if (out_rows) HIP_TRY(hipMemcpyAsync(out_rows, v, sizeof(float) * (size_t)rows, hipMemcpyDeviceToHost, a->s));
+    HIP_TRY(hipStreamSynchronize(a->s));
+    *total += part;
+    return 0;
+}
+
+enum AePredict { AE_RECONSTRUCT, AE_ENCODE, AE_DECODE };
+
+// reconstruct / encode / decode over host rows.
+int ae_predict(vaeb_ae* a, const float* x, int64_t n, float* out, AePredict what) {
     if (!a || !x || !out || n <= 0) return fail(VAEB_ERR_ARG, "bad arguments");
     const vaeb_ae_config& g = a->c;
-    const int win = (what == 2) ? g.Dz : g.Dobs;
-    const int wout = (what == 1) ? g.Dz : g.Dobs;
-    for (int64_t r0 = 0; r0 < n; r0 += g.max_batch) {
-        const int rows = (int)std::min<int64_t>(g.max_batch, n - r0);
-        HIP_TRY(hipMemcpyAsync(a->xin, x + r0 * win, sizeof(float) * (size_t)rows * win, hipMemcpyHostToDevice, a->s));
-        int rc = 0;
-        if (what == 2) rc = ae_forward(a, nullptr, 0, nullptr, rows, false, false, a->xin);
-        else rc = ae_forward(a, a->xin, rows, nullptr, rows, false, what == 1, nullptr);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(out + r0 * wout, what == 1 ? a->Z : a->Xpr, sizeof(float) * (size_t)rows * wout,
+    const int win = (what == AE_DECODE) ? g.Dz : g.Dobs;
+    const int wout = (what == AE_ENCODE) ? g.Dz : g.Dobs;
+    return ae_chunks(a, x, n, win, [&](int64_t r0, int rows) {
+        if (what != AE_DECODE)
+            if (int rc = ae_encode(a, AeRows{a->xin, rows}, rows, AeNoise{})) return rc;
+        if (what != AE_ENCODE) {
+            if (int rc = ae_decode_hidden(a, what == AE_DECODE ? a->xin : a->Z, rows)) return rc;
+            if (int rc = ae_output(a, rows, AE_OUT_PREDICT)) return rc;
+        }
+        HIP_TRY(hipMemcpyAsync(out + r0 * wout, what == AE_ENCODE ? a->Z : a->Xpr, sizeof(float) * (size_t)rows * wout,
                                hipMemcpyDeviceToHost, a->s));
         HIP_TRY(hipStreamSynchronize(a->s));
-    }
-    return 0;
+        return 0;
+    });
 }
 
 int ae_xfer(vaeb_ae* a, float* dev, const float* hin, float* hout, int64_t n) {
@@ -404,76 +452,56 @@ int vaeb_ae_create(const vaeb_ae_config* cfg, vaeb_ae** out) {
         delete a;
         return fail(VAEB_ERR_HIP, "device / stream init failed");
     }
-    a->de.push_back(g.Dobs);
-    for (int i = 0; i < g.n_enc; ++i) a->de.push_back(g.Denc[i]);
-    a->dd.push_back(g.Dz);
-    for (int i = 0; i < g.n_dec; ++i) a->dd.push_back(g.Ddec[i]);
-    // theta order (ae.py:51,56,64,72)
+    for (int i = 0; i < g.n_enc; ++i) { a->enc[i].K = i ? g.Denc[i - 1] : g.Dobs; a->enc[i].N = g.Denc[i]; }
+    for (int i = 0; i < g.n_dec; ++i) { a->dec[i].K = i ? g.Ddec[i - 1] : g.Dz; a->dec[i].N = g.Ddec[i]; }
+    a->lat.n = ae_gauss(a) ? 2 : 1;              // Wz, or as the cont output: Wzmu, Wzlv
+    a->out.n = g.otype == VAEB_AE_CONT ? 2 : 1;  // binary and se: Wout; cont: Wmu, Wlogs2
+    for (int j = 0; j < 2; ++j) {
+        a->lat.l[j].K = g.Denc[g.n_enc - 1]; a->lat.l[j].N = g.Dz;
+        a->out.l[j].K = g.Ddec[g.n_dec - 1]; a->out.l[j].N = g.Dobs;
+    }
+    // theta order (ae.py:51,56,64,72): encoder, latent, decoder, output; each group's W's, then its b's
     int64_t o = 0;
-    for (int i = 0; i < g.n_enc; ++i) { a->oWe.push_back(o); o += (int64_t)a->de[i] * a->de[i + 1]; }
-    for (int i = 0; i < g.n_enc; ++i) { a->obe.push_back(o); o += a->de[i + 1]; }
-    const int64_t HZ = (int64_t)a->de[g.n_enc] * g.Dz;
-    if (g.latent == VAEB_AE_LATENT_GAUSS) {   // as the cont output: Wzmu, Wzlv, bzmu, bzlv
-        a->oWz = o; o += HZ;
-        a->oWzl = o; o += HZ;
-        a->obz = o; o += g.Dz;
-        a->obzl = o; o += g.Dz;
-    } else {
-        a->oWz = o; o += HZ;
-        a->obz = o; o += g.Dz;
-    }
-    for (int i = 0; i < g.n_dec; ++i) { a->oWd.push_back(o); o += (int64_t)a->dd[i] * a->dd[i + 1]; }
-    for (int i = 0; i < g.n_dec; ++i) { a->obd.push_back(o); o += a->dd[i + 1]; }
-    const int64_t HD = (int64_t)a->dd[g.n_dec] * g.Dobs;
-    if (g.otype != VAEB_AE_CONT) {   // binary and se: Wout, bout
-        a->oWo = o; o += HD;
-        a->obo = o; o += g.Dobs;
-    } else {
-        a->oWo = o; o += HD;        // Wmu
-        a->oWl = o; o += HD;        // Wlogs2
-        a->obo = o; o += g.Dobs;    // bmu
-        a->obl = o; o += g.Dobs;    // blogs2
-    }
+    auto place = [&o](AeLayer* l, int n) {
+        for (int i = 0; i < n; ++i) { l[i].oW = o; o += (int64_t)l[i].K * l[i].N; }
+        for (int i = 0; i < n; ++i) { l[i].ob = o; o += l[i].N; }
+    };
+    place(a->enc, g.n_enc);
+    place(a->lat.l, a->lat.n);
+    place(a->dec, g.n_dec);
+    place(a->out.l, a->out.n);
     a->P = o;
     const int64_t B = g.max_batch;
     int rc = 0;
-    rc = rc ? rc : ae_alloc(&a->theta, a->P);
-    rc = rc ? rc : ae_alloc(&a->acc, a->P);
-    a->H.assign(g.n_enc + 1, nullptr);
-    a->dH.assign(g.n_enc + 1, nullptr);
-    a->G.assign(g.n_dec + 1, nullptr);
-    a->dG.assign(g.n_dec + 1, nullptr);
+    rc = rc ? rc : ae_alloc(a, &a->theta, a->P);
+    rc = rc ? rc : ae_alloc(a, &a->acc, a->P);
     for (int i = 1; i <= g.n_enc; ++i) {
-        rc = rc ? rc : ae_alloc(&a->H[i], B * a->de[i]);
-        rc = rc ? rc : ae_alloc(&a->dH[i], B * a->de[i]);
+        rc = rc ? rc : ae_alloc(a, &a->H[i], B * a->enc[i - 1].N);
+        rc = rc ? rc : ae_alloc(a, &a->dH[i], B * a->enc[i - 1].N);
     }
     for (int i = 1; i <= g.n_dec; ++i) {
-        rc = rc ? rc : ae_alloc(&a->G[i], B * a->dd[i]);
-        rc = rc ? rc : ae_alloc(&a->dG[i], B * a->dd[i]);
+        rc = rc ? rc : ae_alloc(a, &a->G[i], B * a->dec[i - 1].N);
+        rc = rc ? rc : ae_alloc(a, &a->dG[i], B * a->dec[i - 1].N);
     }
-    rc = rc ? rc : ae_alloc(&a->Z, B * g.Dz);
-    rc = rc ? rc : ae_alloc(&a->dZ, B * g.Dz);
-    rc = rc ? rc : ae_alloc(&a->Xpr, B * g.Dobs);
-    rc = rc ? rc : ae_alloc(&a->ls2, B * g.Dobs);
-    rc = rc ? rc : ae_alloc(&a->dA, B * g.Dobs);
-    rc = rc ? rc : ae_alloc(&a->dA2, B * g.Dobs);
-    rc = rc ? rc : ae_alloc(&a->ll, B * cdiv(g.Dobs, 16));
-    rc = rc ? rc : ae_alloc(&a->xin, B * std::max(g.Dobs, g.Dz));
+    for (float** p : {&a->Z, &a->dZ}) rc = rc ? rc : ae_alloc(a, p, B * g.Dz);
+    // ls2 and dA2 on every output type
+    for (float** p : {&a->Xpr, &a->ls2, &a->dA, &a->dA2}) rc = rc ? rc : ae_alloc(a, p, B * g.Dobs);
+    rc = rc ? rc : ae_alloc(a, &a->ll, B * cdiv(g.Dobs, 16));
+    rc = rc ? rc : ae_alloc(a, &a->xin, B * std::max(g.Dobs, g.Dz));
     if (ae_gauss(a)) {
-        rc = rc ? rc : ae_alloc(&a->mu, B * g.Dz);
-        rc = rc ? rc : ae_alloc(&a->lv, B * g.Dz);
-        rc = rc ? rc : ae_alloc(&a->dmu, B * g.Dz);
-        rc = rc ? rc : ae_alloc(&a->dlv, B * g.Dz);
-        rc = rc ? rc : ae_alloc(&a->kl, B * cdiv(g.Dz, 16));
-        rc = rc ? rc : dalloc(&a->esum, 1);
+        for (float** p : {&a->mu, &a->lv, &a->dmu, &a->dlv}) rc = rc ? rc : ae_alloc(a, p, B * g.Dz);
+        rc = rc ? rc : ae_alloc(a, &a->kl, B * cdiv(g.Dz, 16));
+        rc = rc ? rc : ae_alloc(a, &a->esum, 1);
     }
     if (ae_iw(a)) {
         rc = rc ? rc : ae_iw_scratch(a);
-        rc = rc ? rc : ae_alloc(&a->iw_wt, B);
-        rc = rc ? rc : ae_alloc(&a->iw_val, B);
-        rc = rc ? rc : dalloc(&a->iw_lw, (size_t)B);
+        rc = rc ? rc : ae_alloc(a, &a->iw_wt, B);
+        rc = rc ? rc : ae_alloc(a, &a->iw_val, B);
+        rc = rc ? rc : ae_alloc(a, &a->iw_lw, B);
     }
     rc = rc ? rc : ae_reserve(a, (int)B, 1);
+    a->out.d[0] = a->dA; a->out.d[1] = a->dA2;
+    a->lat.d[0] = ae_gauss(a) ? a->dmu : a->dZ; a->lat.d[1] = a->dlv;
     if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(VAEB_ERR_HIP, "device init failed");
     if (rc) { vaeb_ae_destroy(a); return rc; }
     *out = a;
@@ -483,15 +511,7 @@ int vaeb_ae_create(const vaeb_ae_config* cfg, vaeb_ae** out) {
 int vaeb_ae_destroy(vaeb_ae* a) {
     if (!a) return 0;
     if (a->s) hipStreamSynchronize(a->s);
-    std::vector<float*> ps = {a->theta, a->acc, a->data, a->Z, a->dZ, a->Xpr, a->ls2, a->dA, a->dA2, a->ll, a->outs,
-                              a->xin, a->mu, a->lv, a->dmu, a->dlv, a->kl, a->eps_in, a->iw, a->iw_wt, a->iw_val,
-                              a->sq_rows};
-    for (auto* v : {&a->H, &a->G, &a->dH, &a->dG}) ps.insert(ps.end(), v->begin(), v->end());
-    for (float* p : ps) if (p) hipFree(p);
-    if (a->idx) hipFree(a->idx);
-    if (a->iw_yrow) hipFree(a->iw_yrow);
-    if (a->esum) hipFree(a->esum);
-    if (a->iw_lw) hipFree(a->iw_lw);
+    for (void* p : a->owned) hipFree(p);
     if (a->s) hipStreamDestroy(a->s);
     delete a;
     return 0;
@@ -506,8 +526,7 @@ int vaeb_ae_num_params(const vaeb_ae* a, int64_t* n) {
 int vaeb_ae_set_data(vaeb_ae* a, const float* x, int64_t n_rows) {
     if (!a || !x || n_rows <= 0) return fail(VAEB_ERR_ARG, "bad data arguments");
     HIP_TRY(hipStreamSynchronize(a->s));
-    if (a->data) { hipFree(a->data); a->data = nullptr; }
-    if (int rc = dalloc(&a->data, (size_t)n_rows * a->c.Dobs)) return rc;
+    if (int rc = ae_realloc(a, &a->data, n_rows * a->c.Dobs)) return rc;
     HIP_TRY(hipMemcpy(a->data, x, sizeof(float) * (size_t)n_rows * a->c.Dobs, hipMemcpyHostToDevice));
     a->nrows = n_rows;
     return 0;
@@ -522,24 +541,18 @@ int vaeb_ae_train_many(vaeb_ae* a, const int32_t* idx, int32_t n, int32_t batch,
     if (!a || !idx || !out || n <= 0 || batch <= 0) return fail(VAEB_ERR_ARG, "bad arguments");
     if (batch > a->c.max_batch) return fail(VAEB_ERR_ARG, "batch %d > max_batch %d", batch, a->c.max_batch);
     if (int rc = ae_check_idx(a, idx, n)) return rc;
-    const bool gauss = ae_gauss(a), iw = ae_iw(a);
+    const bool iw = ae_iw(a);
     if (iw && (int64_t)a->c.iw_samples * std::min(batch, n) > a->c.max_batch)
         return fail(VAEB_ERR_ARG, "iw_samples %d x batch %d > max_batch %d (the stacked sample planes)",
                     a->c.iw_samples, std::min(batch, n), a->c.max_batch);
-    if (gauss)
+    if (ae_gauss(a))
         if (int rc = ae_host_eps_ready(a, iw ? (int64_t)a->c.iw_samples * n : (int64_t)n)) return rc;
     const int nb = cdiv(n, batch);
     if (int rc = ae_reserve(a, n, nb)) return rc;
     HIP_TRY(hipMemcpyAsync(a->idx, idx, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, a->s));
     for (int j = 0; j < nb; ++j) {
         const int lb = j * batch, m = std::min(batch, n - lb);
-        if (iw) {
-            if (int rc = ae_step_iw(a, a->idx + lb, m, j, lb, n, a->step)) return rc;
-            ++a->step;
-        } else if (gauss) {   // each step draws at the counter, then advances it
-            if (int rc = ae_step(a, a->idx + lb, m, j, ae_noise(a, a->idx + lb, lb, a->step, false))) return rc;
-            ++a->step;
-        } else if (int rc = ae_step(a, a->idx + lb, m, j)) return rc;
+        if (int rc = ae_step(a, a->idx + lb, m, j, lb, n)) return rc;
     }
     HIP_TRY(hipMemcpyAsync(out, a->outs, sizeof(float) * (size_t)nb, hipMemcpyDeviceToHost, a->s));
     HIP_TRY(hipStreamSynchronize(a->s));
@@ -551,38 +564,27 @@ int vaeb_ae_train(vaeb_ae* a, const int32_t* idx, int32_t n, float* out) {
     return vaeb_ae_train_many(a, idx, n, n, out);
 }
 
-int vaeb_ae_reconstruct(vaeb_ae* a, const float* x, int64_t n, float* out) { return ae_predict(a, x, n, out, 0); }
-int vaeb_ae_encode(vaeb_ae* a, const float* x, int64_t n, float* z) { return ae_predict(a, x, n, z, 1); }
-int vaeb_ae_decode(vaeb_ae* a, const float* z, int64_t n, float* out) { return ae_predict(a, z, n, out, 2); }
+int vaeb_ae_reconstruct(vaeb_ae* a, const float* x, int64_t n, float* out) { return ae_predict(a, x, n, out, AE_RECONSTRUCT); }
+int vaeb_ae_encode(vaeb_ae* a, const float* x, int64_t n, float* z) { return ae_predict(a, x, n, z, AE_ENCODE); }
+int vaeb_ae_decode(vaeb_ae* a, const float* z, int64_t n, float* out) { return ae_predict(a, z, n, out, AE_DECODE); }
 
 int vaeb_ae_sq_error(vaeb_ae* a, const float* x, int64_t n, double* out_sum, float* out_rows) {
     if (!a || !x || !out_sum || n <= 0) return fail(VAEB_ERR_ARG, "bad arguments");
     const vaeb_ae_config& g = a->c;
-    const int nct = cdiv(g.Dobs, 16);
-    if (!a->sq_rows)
-        if (int rc = ae_alloc(&a->sq_rows, g.max_batch)) return rc;
-    if (!a->esum)
-        if (int rc = dalloc(&a->esum, 1)) return rc;
+    if (int rc = ae_lazy(a, &a->sq_rows, g.max_batch)) return rc;
+    if (int rc = ae_lazy(a, &a->esum, 1)) return rc;
     double total = 0.0;
-    for (int64_t r0 = 0; r0 < n; r0 += g.max_batch) {
-        const int rows = (int)std::min<int64_t>(g.max_batch, n - r0);
-        HIP_TRY(hipMemcpyAsync(a->xin, x + r0 * g.Dobs, sizeof(float) * (size_t)rows * g.Dobs, hipMemcpyHostToDevice,
-                               a->s));
-        // the deterministic forward (Gaussian latent: z = mu), then the mean head's (Y - P)^2 partials
-        if (int rc = ae_forward(a, a->xin, rows, nullptr, rows, true, false, nullptr, AeNoise{}, true, true)) return rc;
-        hipLaunchKernelGGL(ae::ae_row_sum_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, a->s, a->ll, rows, nct,
-                           a->sq_rows);
-        CHECK_LAUNCH();
-        HIP_TRY(hipMemsetAsync(a->esum, 0, sizeof(double), a->s));
-        hipLaunchKernelGGL(iw_sum_kernel, dim3(1), dim3(256), 0, a->s, a->sq_rows, (int64_t)rows, a->esum);
-        CHECK_LAUNCH();
-        double part = 0.0;
-        HIP_TRY(hipMemcpyAsync(&part, a->esum, sizeof(double), hipMemcpyDeviceToHost, a->s));
-        if (out_rows)
-            HIP_TRY(hipMemcpyAsync(out_rows + r0, a->sq_rows, sizeof(float) * (size_t)rows, hipMemcpyDeviceToHost, a->s));
-        HIP_TRY(hipStreamSynchronize(a->s));
-        total += part;
-    }
+    if (int rc = ae_chunks(a, x, n, g.Dobs, [&](int64_t r0, int rows) {
+            // the deterministic forward (Gaussian latent: z = mu), then the mean head's (Y - P)^2 partials
+            const AeRows xc{a->xin, rows};
+            if (int rc = ae_encode(a, xc, rows, AeNoise{})) return rc;
+            if (int rc = ae_decode_hidden(a, a->Z, rows)) return rc;
+            if (int rc = ae_output(a, rows, AE_OUT_SQ, xc)) return rc;
+            hipLaunchKernelGGL(ae::ae_row_sum_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, a->s, a->ll, rows,
+                               cdiv(g.Dobs, 16), a->sq_rows);
+            CHECK_LAUNCH();
+            return ae_sum_to_host(a, a->sq_rows, rows, &total, out_rows ? out_rows + r0 : nullptr);
+        })) return rc;
     *out_sum = total;
     return 0;
 }
@@ -608,13 +610,8 @@ int vaeb_ae_push_eps(vaeb_ae* a, const float* eps, int64_t rows) {
     if (!eps || rows <= 0) return fail(VAEB_ERR_ARG, "bad eps arguments");
     const int64_t n = rows * a->c.Dz;
     HIP_TRY(hipStreamSynchronize(a->s));
-    if (n > a->eps_cap) {
-        if (a->eps_in) hipFree(a->eps_in);
-        a->eps_in = nullptr;
-        a->eps_cap = a->eps_rows = 0;
-        if (int rc = dalloc(&a->eps_in, (size_t)n)) return rc;
-        a->eps_cap = n;
-    }
+    if (n > a->eps_cap) a->eps_rows = 0;   // the old rows go with the old buffer
+    if (int rc = ae_grow(a, &a->eps_in, &a->eps_cap, n)) return rc;
     HIP_TRY(hipMemcpy(a->eps_in, eps, sizeof(float) * (size_t)n, hipMemcpyHostToDevice));
     a->eps_rows = rows;
     return 0;
@@ -639,19 +636,16 @@ int vaeb_ae_encode_dist(vaeb_ae* a, const float* x, int64_t n, float* out_mu, fl
     const vaeb_ae_config& g = a->c;
     if (out_z)
         if (int rc = ae_host_eps_ready(a, n)) return rc;
-    for (int64_t r0 = 0; r0 < n; r0 += g.max_batch) {
-        const int rows = (int)std::min<int64_t>(g.max_batch, n - r0);
-        HIP_TRY(hipMemcpyAsync(a->xin, x + r0 * g.Dobs, sizeof(float) * (size_t)rows * g.Dobs, hipMemcpyHostToDevice,
-                               a->s));
-        const AeNoise nz = out_z ? ae_noise(a, nullptr, r0, a->step, true) : AeNoise{};
-        if (int rc = ae_forward(a, a->xin, rows, nullptr, rows, false, true, nullptr, nz)) return rc;
+    return ae_chunks(a, x, n, g.Dobs, [&](int64_t r0, int rows) {
+        if (int rc = ae_encode(a, AeRows{a->xin, rows}, rows, AeNoise{out_z ? AE_EPS_EVAL : AE_EPS_ZERO, nullptr, r0}))
+            return rc;
         const size_t nb = sizeof(float) * (size_t)rows * g.Dz;
         if (out_mu) HIP_TRY(hipMemcpyAsync(out_mu + r0 * g.Dz, a->mu, nb, hipMemcpyDeviceToHost, a->s));
         if (out_lv) HIP_TRY(hipMemcpyAsync(out_lv + r0 * g.Dz, a->lv, nb, hipMemcpyDeviceToHost, a->s));
         if (out_z) HIP_TRY(hipMemcpyAsync(out_z + r0 * g.Dz, a->Z, nb, hipMemcpyDeviceToHost, a->s));
         HIP_TRY(hipStreamSynchronize(a->s));
-    }
-    return 0;
+        return 0;
+    });
 }
 
 int vaeb_ae_elbo(vaeb_ae* a, const float* x, int64_t n, double* out_sum) {
@@ -660,20 +654,17 @@ int vaeb_ae_elbo(vaeb_ae* a, const float* x, int64_t n, double* out_sum) {
     const vaeb_ae_config& g = a->c;
     if (int rc = ae_host_eps_ready(a, n)) return rc;
     double total = 0.0;
-    for (int64_t r0 = 0; r0 < n; r0 += g.max_batch) {
-        const int rows = (int)std::min<int64_t>(g.max_batch, n - r0);
-        HIP_TRY(hipMemcpyAsync(a->xin, x + r0 * g.Dobs, sizeof(float) * (size_t)rows * g.Dobs, hipMemcpyHostToDevice,
-                               a->s));
-        if (int rc = ae_forward(a, a->xin, rows, nullptr, rows, true, false, nullptr,
-                                ae_noise(a, nullptr, r0, a->step, true))) return rc;
-        hipLaunchKernelGGL(ae::ae_elbo_kernel, dim3(1), dim3(256), 0, a->s, a->ll, (int64_t)rows * cdiv(g.Dobs, 16),
-                           a->kl, (int64_t)rows * cdiv(g.Dz, 16), rows, (float*)nullptr, 0, a->esum);
-        CHECK_LAUNCH();
-        double part = 0.0;
-        HIP_TRY(hipMemcpyAsync(&part, a->esum, sizeof(double), hipMemcpyDeviceToHost, a->s));
-        HIP_TRY(hipStreamSynchronize(a->s));
-        total += part;
-    }
+    if (int rc = ae_chunks(a, x, n, g.Dobs, [&](int64_t r0, int rows) {
+            const AeRows xc{a->xin, rows};
+            if (int rc = ae_encode(a, xc, rows, AeNoise{AE_EPS_EVAL, nullptr, r0})) return rc;
+            if (int rc = ae_decode_hidden(a, a->Z, rows)) return rc;
+            if (int rc = ae_output(a, rows, AE_OUT_TRAIN, xc)) return rc;
+            // writes esum itself: no memset
+            hipLaunchKernelGGL(ae::ae_elbo_kernel, dim3(1), dim3(256), 0, a->s, a->ll, (int64_t)rows * cdiv(g.Dobs, 16),
+                               a->kl, (int64_t)rows * cdiv(g.Dz, 16), rows, (float*)nullptr, 0, a->esum);
+            CHECK_LAUNCH();
+            return ae_sum_to_host(a, nullptr, 0, &total);
+        })) return rc;
     *out_sum = total;
     return 0;
 }
@@ -685,10 +676,10 @@ int vaeb_ae_marginal_ll(vaeb_ae* a, const float* x, int64_t n, int32_t K, double
         return fail(VAEB_ERR_ARG, "K = %d: 1 to 2^20 samples (the Philox sample-stream field)", K);
     if (int rc = ae_host_eps_ready(a, n * K)) return rc;
     const vaeb_ae_config& g = a->c;
-    const int B = g.max_batch, nct = cdiv(g.Dobs, 16);
+    const int B = g.max_batch;
     if (int rc = ae_iw_scratch(a)) return rc;
     IwArgs w{};
-    w.nctD = nct; w.K = K; w.logK = (float)std::log((double)K);
+    w.nctD = cdiv(g.Dobs, 16); w.K = K; w.logK = (float)std::log((double)K);
     w.lat = a->iw; w.ms = a->iw + B; w.rows = a->iw + 3 * (int64_t)B; w.lp_part = a->ll;
     ae::AeIwArgs q{};
     q.Dz = g.Dz; q.n = n;
@@ -696,32 +687,23 @@ int vaeb_ae_marginal_ll(vaeb_ae* a, const float* x, int64_t n, int32_t K, double
     q.seed = a->seed; q.step = a->step; q.eps_in = a->eps_in;
     q.mu = a->mu; q.lv = a->lv; q.z = a->Z; q.lat = a->iw; q.yrow = a->iw_yrow;
     double total = 0.0;
-    for (int64_t r0 = 0; r0 < n; r0 += B) {
-        const int R = (int)std::min<int64_t>(B, n - r0);
-        HIP_TRY(hipMemcpyAsync(a->xin, x + r0 * g.Dobs, sizeof(float) * (size_t)R * g.Dobs, hipMemcpyHostToDevice, a->s));
-        if (int rc = ae_forward(a, a->xin, R, nullptr, R, false, true, nullptr)) return rc;   // mu, lv: once
-        const int smax = std::max(1, B / R);   // sample planes per pass: S * R <= max_batch stacked rows
-        w.Mb = w.Mbp = q.R = R;
-        q.row0 = r0;
-        for (int k0 = 0; k0 < K; k0 += smax) {
-            const int S = std::min(smax, K - k0);
-            w.k0 = q.k0 = k0; w.S = q.S = S;
-            hipLaunchKernelGGL(ae::ae_iw_sample_kernel, dim3(cdiv(S * R, 16)), dim3(256), 0, a->s, q);
-            CHECK_LAUNCH();
-            if (int rc = ae_forward(a, a->xin, R, a->iw_yrow, S * R, true, false, a->Z, AeNoise{}, true)) return rc;
-            hipLaunchKernelGGL(iw_lse_kernel, dim3(cdiv(R, 256)), dim3(256), 0, a->s, w);
-            CHECK_LAUNCH();
-        }
-        HIP_TRY(hipMemsetAsync(a->esum, 0, sizeof(double), a->s));
-        hipLaunchKernelGGL(iw_sum_kernel, dim3(1), dim3(256), 0, a->s, w.rows, (int64_t)R, a->esum);
-        CHECK_LAUNCH();
-        double part = 0.0;
-        HIP_TRY(hipMemcpyAsync(&part, a->esum, sizeof(double), hipMemcpyDeviceToHost, a->s));
-        if (out_rows)
-            HIP_TRY(hipMemcpyAsync(out_rows + r0, w.rows, sizeof(float) * (size_t)R, hipMemcpyDeviceToHost, a->s));
-        HIP_TRY(hipStreamSynchronize(a->s));
-        total += part;
-    }
+    if (int rc = ae_chunks(a, x, n, g.Dobs, [&](int64_t r0, int R) {
+            if (int rc = ae_encode(a, AeRows{a->xin, R}, R, AeNoise{})) return rc;   // mu, lv: once
+            const int smax = std::max(1, B / R);   // sample planes per pass: S * R <= max_batch stacked rows
+            w.Mb = w.Mbp = q.R = R;
+            q.row0 = r0;
+            for (int k0 = 0; k0 < K; k0 += smax) {
+                const int S = std::min(smax, K - k0);
+                w.k0 = q.k0 = k0; w.S = q.S = S;
+                hipLaunchKernelGGL(ae::ae_iw_sample_kernel, dim3(cdiv(S * R, 16)), dim3(256), 0, a->s, q);
+                CHECK_LAUNCH();
+                if (int rc = ae_decode_hidden(a, a->Z, S * R)) return rc;
+                if (int rc = ae_output(a, S * R, AE_OUT_VALUE, AeRows{a->xin, R, a->iw_yrow})) return rc;
+                hipLaunchKernelGGL(iw_lse_kernel, dim3(cdiv(R, 256)), dim3(256), 0, a->s, w);
+                CHECK_LAUNCH();
+            }
+            return ae_sum_to_host(a, w.rows, R, &total, out_rows ? out_rows + r0 : nullptr);
+        })) return rc;
     *out_sum = total;
     return 0;
 }
