@@ -525,3 +525,25 @@ def test_gemm8_two_slices_combined_in_launch(gctx, ako, bko, M, N, K):
     bound = 1e-5 * (np.abs(Aq) @ np.abs(Bq)) + 1e-30
     assert np.all(np.abs(C - ref) <= bound), float(np.max(np.abs(C - ref) / bound))
     assert np.array_equal(C, gctx.test_gemm_bf16(As, Bs, ako, bko, M, N, K, -22))
+
+
+PROFILE_SLOTS = ["bf_enc", "bf_heads", "bf_latent", "bf_dechid", "bf_decout", "bf_dhd_dW26", "bf_dz", "bf_dW1",
+                 "bf_dW1_opt", "bf_latent_bwd", "bf_dh", "bf_dW45", "bf_dW45_opt", "bf_dW3", "bf_bias_elbo"]
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "fp16"])
+@pytest.mark.parametrize("D,H,Z,B,absent", [(256, 128, 32, 256, ()), (264, 200, 128, 200, ("bf_latent", "bf_dz"))],
+                         ids=["split_k_latent", "thin"])
+def test_h16_profile_slots(D, H, Z, B, absent, dtype):
+    """The profiled 16-bit step (vaeb_profile_steps: unforked, dhd and dW2 in one grid, every
+    launch repeated inside its event bracket) reports one slot per launch group, in launch
+    order; the thin launches (Z % 128 == 0) carry the latent forward in bf_heads and dz in
+    bf_latent_bwd, so those two slots are absent there.  Every time is finite and positive."""
+    from vaeb_amd import _lib
+    ctx = _lib.Context(D, H, Z, B, max_eval_rows=B, dtype=_lib.DTYPE_BF16 if dtype == "bf16" else _lib.DTYPE_F16)
+    ctx.set_data(O.synthetic_mnist(n=2 * B, D=D))
+    ctx.set_params(O.flatten(O.init_params(O.Config(D=D, H=H, Z=Z))))
+    prof = ctx.profile_steps(1)
+    ctx.close()
+    assert [n for n, _ in prof] == [s for s in PROFILE_SLOTS if s not in absent]
+    assert all(np.isfinite(ms) and ms > 0 for _, ms in prof), prof

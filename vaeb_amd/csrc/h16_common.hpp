@@ -2,6 +2,8 @@
 // what the host keeps per context and what the kernels of both instantiations (h16_engines.hpp)
 // share.  16-bit values are raw bits in memory (uint16_t) in either format.
 #pragma once
+#include <vector>
+
 #include "tile_engine.hpp"
 
 namespace vaeb {
@@ -40,7 +42,6 @@ struct ShadowMap {
 
 // Device buffers of the 16-bit engine (one context).  Row capacity R = max(B, eval chunk).
 struct BfState {
-    bool on = false;
     int Dn = 0;                        // decoder output width (D, or 2D interleaved)
     int64_t S = 0;                     // shadow elements
     int64_t s3 = 0, s45 = 0, s1 = 0, s26 = 0;
@@ -63,6 +64,7 @@ struct BfState {
     bool thin_h = false, thin_z = false;   // heads / dz on the thin launches
     int nkl = 1;
     ShadowMap smap{};
+    std::vector<void*> owned;          // host: the engine's device allocations (bf_alloc; freed by bf_free)
 };
 
 }  // namespace h16c

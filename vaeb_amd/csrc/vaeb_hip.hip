@@ -188,7 +188,7 @@ struct vaeb_ctx {
     ncclComm_t comm = nullptr;
     int rank = 0, world = 1;
     hipStream_t s3 = nullptr;     // bf16 engine: dW2 (| dW6) + Adagrad forked beside the backward chain
-    hipEvent_t fk_ev[4] = {};     // fork after dhd, s3's work done, [dMu | dLv] ready, ELBO partials
+    hipEvent_t fk_ev[3] = {};     // fork after dhd, s3's work done, [dMu | dLv] ready
     int bf_thin = 3;              // VAEB_BF_THIN mask: 1 heads, 2 dz on thin_bf16.hpp (0: split-K + latent kernels)
     bool bf_fork = true;          // VAEB_BF_FORK=0: dW2 in the dhd grid (bf_fuse) or after it
     int bf_dzfuse = 1;            // VAEB_BF_DZFUSE=0: dz + latent backward on the thin launch instead of in the forked dhd
@@ -306,6 +306,17 @@ struct BfFwd {
     const float* eps_in; int64_t eps_in_ld; uint32_t domain;
     float* yout;
 };
+// An evaluation forward (no stores for a backward) of `rows` rows at x, global rows from r0 (the
+// noise keys and the host eps rows), evaluation noise `domain`.
+BfFwd bf_eval_fwd(const vaeb_ctx* c, const bf16_t* x, int rows, int64_t r0, int mode, const float* eps_in, uint32_t domain,
+                  float* yout) {
+    BfFwd f{};
+    f.Mb = rows; f.mode = mode; f.train = false; f.x = x; f.xb = h16c::BatchRef{};
+    f.row_base_mul = 0; f.row_base_add = r0;
+    f.eps_in = eps_in; f.eps_in_ld = c->eps_rows; f.domain = domain;
+    f.yout = yout;
+    return f;
+}
 namespace eng_bf {
 namespace bf = ::vaeb::bf;
 constexpr bool kF16 = false;
@@ -487,6 +498,7 @@ int vaeb_create(const vaeb_config* cfg, vaeb_ctx** out) {
     if (g.dtype != VAEB_DTYPE_F32 && g.dtype != VAEB_DTYPE_BF16 && g.dtype != VAEB_DTYPE_F16)
         return fail(VAEB_ERR_ARG, "bad dtype %d", g.dtype);
     if (g.dtype == VAEB_DTYPE_BF16 || g.dtype == VAEB_DTYPE_F16) {
+        // (engine_bf16.inc relies on this check: it tests none of D, H, Z % 8 again)
         if (g.D % 8 || g.H % 8 || g.Z % 8)
             return fail(VAEB_ERR_ARG, "bf16 engine: D, H, Z must be multiples of 8 (got %d, %d, %d)", g.D, g.H, g.Z);
         if (g.decoder == VAEB_DEC_GAUSSIAN && g.D % 32)
@@ -581,8 +593,7 @@ int vaeb_create(const vaeb_config* cfg, vaeb_ctx** out) {
         if (hipStreamCreateWithFlags(&c->s3, hipStreamNonBlocking) != hipSuccess ||
             hipEventCreateWithFlags(&c->fk_ev[0], hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&c->fk_ev[1], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&c->fk_ev[2], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&c->fk_ev[3], hipEventDisableTiming) != hipSuccess)
+            hipEventCreateWithFlags(&c->fk_ev[2], hipEventDisableTiming) != hipSuccess)
             rc = fail(VAEB_ERR_HIP, "fork stream / events");
     }
     if (rc) { vaeb_destroy(c); return rc; }
@@ -1197,11 +1208,7 @@ int vaeb_reconstruct_full(vaeb_ctx* c, const float* x, int64_t n, int32_t n_samp
             const float* eps = (host && c->eps_in) ? c->eps_in + ((int64_t)sidx * n + r0) * g.Z : nullptr;
             Prof pr{c, false};
             if (is_bf16(c)) {
-                BfFwd f{};
-                f.Mb = rows; f.mode = MODE_EVAL; f.train = false; f.x = c->bf.xeval; f.xb = h16c::BatchRef{};
-                f.row_base_mul = 0; f.row_base_add = r0;
-                f.eps_in = eps; f.eps_in_ld = c->eps_rows; f.domain = domain;
-                f.yout = c->y;
+                const BfFwd f = bf_eval_fwd(c, c->bf.xeval, rows, r0, MODE_EVAL, eps, domain, c->y);
                 if (int rc = bf_forward(c, c->par, f, pr)) return rc;
             } else {
                 StepArgs a = make_args(c, epar, rows, MODE_RECON, c->xeval, false);
