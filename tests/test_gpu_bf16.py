@@ -547,3 +547,56 @@ def test_h16_profile_slots(D, H, Z, B, absent, dtype):
     ctx.close()
     assert [n for n, _ in prof] == [s for s in PROFILE_SLOTS if s not in absent]
     assert all(np.isfinite(ms) and ms > 0 for _, ms in prof), prof
+
+
+def h16_resident_sampled_and_refusals(dtype, q, y_tol, gauss):
+    """Shared with tests/test_gpu_fp16.py: what test_*_validate_and_reconstruct leaves out -- the
+    resident validation set, sampled reconstruction on the device's own draws, and the calls a
+    16-bit context refuses -- at 256-128-32 (Bernoulli) or 256-96-16 (Gaussian), max_eval_rows = 64 over 2 * 64 + 7 rows (three chunks, the last
+    neither full nor a multiple of 16).  Oracle and tolerances as there: validate 1e-4 relative to the
+    oracle rounding like the engine (q); sampled decoder means y_tol against the float64 oracle."""
+    from oracle import philox as P
+    from vaeb_amd import _lib
+    cfg = O.Config(D=256, H=96, Z=16, continuous=True) if gauss else O.Config(D=256, H=128, Z=32)
+    n, seed, step = 2 * 64 + 7, (33 << 32) | 0x1234567, 5
+    x = data_for(cfg, n)
+    params = O.init_params(cfg)
+    p64, x64 = [p.astype(np.float64) for p in params], x.astype(np.float64)
+    ctx = _lib.Context(cfg.D, cfg.H, cfg.Z, 64, decoder=int(gauss), max_eval_rows=64, dtype=dtype)
+    try:
+        ctx.set_params(O.flatten(params))
+        ctx.set_valid_data(x)
+        ctx.set_eps_mode(_lib.EPS_HOST)
+        eps = np.random.default_rng(1).standard_normal((1, n, cfg.Z)).astype(np.float32)
+        ctx.push_eps(eps)
+        ref = O.validate(p64, x64, eps.astype(np.float64), cfg, q=q)
+        for got in (ctx.validate(x), ctx.validate_resident()):
+            assert abs(got - ref) <= 1e-4 * abs(ref), (got, ref)
+        eps3 = np.random.default_rng(2).standard_normal((3, n, cfg.Z)).astype(np.float32)
+        ctx.push_eps(eps3.reshape(1, 3 * n, cfg.Z))
+        ys = ctx.reconstruct_sampled(x, 3)
+        assert np.abs(ys - O.reconstruct(p64, x64, eps3.astype(np.float64), cfg)).max() <= y_tol
+        ctx.set_eps_mode(_lib.EPS_PHILOX, seed)
+        ctx.set_step(step)
+        ref = O.validate(p64, x64, P.eval_eps(seed, step, n, cfg.Z, 0)[None], cfg, q=q)
+        for got in (ctx.validate(x), ctx.validate_resident()):
+            assert abs(got - ref) <= 1e-4 * abs(ref), (got, ref)
+        ys = ctx.reconstruct_sampled(x, 3)
+        epsp = np.stack([P.eval_eps(seed, step, n, cfg.Z, s) for s in (1, 2, 3)])
+        assert np.abs(ys - O.reconstruct(p64, x64, epsp, cfg)).max() <= y_tol
+        z = np.zeros((n, cfg.Z), np.float32)
+        for fn, a in ((ctx.decode, (z,)), (ctx.encode, (x,)), (ctx.marginal_ll, (x, 3)), (ctx.marginal_ll_resident, (3,))):
+            with pytest.raises(_lib.VaebError, match=r"error -1: .*served by fp32 contexts"):
+                fn(*a)
+        if gauss:
+            with pytest.raises(_lib.VaebError, match=r"error -1: the log-sigma output is served by fp32 contexts"):
+                ctx.reconstruct_full(x, 0)
+        assert abs(ctx.validate_resident() - ref) <= 1e-4 * abs(ref)      # a refusal leaves the context working
+    finally:
+        ctx.close()
+
+
+@pytest.mark.parametrize("gauss", [False, True])
+def test_bf16_resident_sampled_philox_and_refusals(gauss):
+    from vaeb_amd import _lib
+    h16_resident_sampled_and_refusals(_lib.DTYPE_BF16, O.bf16_round, 2e-2, gauss)

@@ -267,3 +267,114 @@ def test_per_row_outputs(name, mer):
                                             for k, (e, t) in errs.items()))
     for k, (e, t) in errs.items():
         assert got[k].shape == out[k].shape and e <= t, (k, e, t)
+
+
+# ------------------------------------------------------------------ FV / FVS contexts, the all-reduce arm
+# The evaluation calls on the full-variational estimators and behind a one-rank communicator, at
+# max_eval_rows = 64 over 2 * 64 + 7 rows (three chunks, the last neither full nor a multiple of
+# 16).  FV evaluates the data term at the loaded theta, FVS at the posterior mean mu_theta (copied
+# into the spare arena per call); theta and mu_theta differ here, so the wrong arena shows.  Oracle
+# functions and tolerances are those of the tests above and of tests/test_gpu_marginal_ll.py
+# (validate: n * data + thetaPrior as tests/test_gpu_step.py::test_fv_weight_sampling_step).
+EVAL_MER, EVAL_N, EVAL_K = 64, 2 * 64 + 7, 5
+EVAL_SHAPES = {"72-40-8": dict(D=72, H=40, Z=8), "64-48-40-gauss": dict(D=64, H=48, Z=40, continuous=True)}
+
+
+@functools.lru_cache(maxsize=None)
+def eval_inputs(shape):
+    """cfg (LB), theta, mu_theta, sigma_theta, x, eps [1, n, Z], eps3 [3, n, Z], epsK [K, n, Z]."""
+    cfg = O.Config(**EVAL_SHAPES[shape])
+    n = EVAL_N
+    rng = np.random.default_rng(3)
+    theta = [(0.1 * rng.standard_normal(s)).astype(np.float32) for _, s in O.param_shapes(cfg)]
+    mu = [(t + 0.05 * rng.standard_normal(t.shape)).astype(np.float32) for t in theta]
+    sig = [np.full_like(t, 1e-3) for t in theta]
+    eps = rng.standard_normal((1, n, cfg.Z)).astype(np.float32)
+    eps3 = rng.standard_normal((3, n, cfg.Z)).astype(np.float32)
+    epsK = rng.standard_normal((EVAL_K, n, cfg.Z)).astype(np.float32)
+    x = (O.synthetic_frey if cfg.continuous else O.synthetic_mnist)(n=n, D=cfg.D, seed=5)
+    for a in [x, eps, eps3, epsK] + theta + mu + sig:
+        a.setflags(write=False)
+    return cfg, theta, mu, sig, x, eps, eps3, epsK
+
+
+def check_eval_calls(ctx, cfg, p, prior_of, x, eps, eps3, epsK, what):
+    """Every evaluation call of ctx against the float64 oracle at parameters p; prior_of: None, or
+    (mu, sigma) of the thetaPrior an FV context adds to n * data."""
+    from tests.test_gpu_marginal_ll import RTOL, assert_matches, iw_reference
+    from vaeb_amd import _lib
+    n = x.shape[0]
+    f64 = lambda q: [a.astype(np.float64) for a in q]   # noqa: E731
+    p64, x64 = f64(p), x.astype(np.float64)
+    out = O.forward_backward(p64, x64, eps.astype(np.float64), cfg, need_grad=False)
+    ref_v = float(out["sgvb"])
+    if prior_of is not None:
+        ref_v = n * ref_v + O.fv_theta_prior(f64(prior_of[0]), f64(prior_of[1]))
+    ctx.set_eps_mode(_lib.EPS_HOST)
+    ctx.push_eps(eps)
+    ctx.set_valid_data(x)
+    sums = {"validate": (ctx.validate(x), ref_v), "validate_resident": (ctx.validate_resident(), ref_v)}
+    ctx.push_eps(stacked(eps3))
+    got = {"recon": ctx.reconstruct(x), "recon3": ctx.reconstruct_sampled(x, 3)}
+    want = {"recon": O.reconstruct(p64, x64, None, cfg), "recon3": O.reconstruct(p64, x64, eps3.astype(np.float64), cfg)}
+    if cfg.continuous:
+        got["full3_mu"], got["full3_ls"] = ctx.reconstruct_full(x, 3)
+        want["full3_mu"], want["full3_ls"] = O.reconstruct_full(p64, x64, eps3.astype(np.float64), cfg)
+    z0 = out["z"][0].astype(np.float32)
+    got["dec_mu"], dec_ls = ctx.decode(z0)
+    want["dec_mu"], want_ls = O.decode(p64, z0.astype(np.float64), cfg)
+    if cfg.continuous:
+        got["dec_ls"], want["dec_ls"] = dec_ls, want_ls
+    got["mu"], got["lv"] = ctx.encode(x)
+    want["mu"], want["lv"] = out["mu"], out["lv"]
+    cfg_la = O.Config(**{**cfg.__dict__, "estimator": "LA"})
+    lw, ref_rows = iw_reference(O.forward_backward(p64, x64, epsK.astype(np.float64), cfg_la, need_grad=False), EVAL_K)
+    ctx.push_eps(stacked(epsK))
+    total, rows = ctx.marginal_ll(x, EVAL_K, rows=True)
+    res = ctx.marginal_ll_resident(EVAL_K)
+    # the device's own draws: validate and the resident form on stream 0
+    ctx.set_eps_mode(_lib.EPS_PHILOX, SEED)
+    ctx.set_step(STEP)
+    ref_p = float(O.validate(p64, x64, planes_eval_eps(SEED, STEP, n, 1, cfg.Z), cfg))
+    if prior_of is not None:
+        ref_p = n * ref_p + O.fv_theta_prior(f64(prior_of[0]), f64(prior_of[1]))
+    sums["philox validate"] = (ctx.validate(x), ref_p)
+    sums["philox resident"] = (ctx.validate_resident(), ref_p)
+    errs = {k: maxabs(v, want[k]) for k, v in got.items()}
+    print(f"{what}: " + ", ".join(f"{k} rel {abs(v - r) / abs(r):.2e}" for k, (v, r) in sums.items()) + "; " +
+          ", ".join(f"{k} {e:.2e}" for k, e in errs.items()))
+    for k, (v, r) in sums.items():
+        assert abs(v - r) <= 1e-4 * abs(r), (what, k, v, r)
+    for k, e in errs.items():
+        assert got[k].shape == want[k].shape and e <= 1e-5, (what, k, e)
+    assert_matches(total, rows, ref_rows, f"{what} marginal_ll")
+    assert abs(res - ref_rows.sum()) <= RTOL * abs(ref_rows.sum()), (what, res, ref_rows.sum())
+
+
+@pytest.mark.parametrize("shape", list(EVAL_SHAPES))
+@pytest.mark.parametrize("est", ["FV", "FVS"])
+def test_full_variational_contexts_evaluate_in_chunks(est, shape):
+    cfg, theta, mu, sig, x, eps, eps3, epsK = eval_inputs(shape)
+    ctx = make_ctx(O.Config(**{**cfg.__dict__, "estimator": est}), B, keep_grads=False, max_eval_rows=EVAL_MER)
+    try:
+        zero = np.zeros_like(O.flatten(theta))
+        ctx.set_params(O.flatten(theta))
+        ctx.set_fv_state(O.flatten(mu), O.flatten(sig), zero, zero)
+        check_eval_calls(ctx, cfg, mu if est == "FVS" else theta, (mu, sig), x, eps, eps3, epsK, f"{est} {shape}")
+        assert np.array_equal(ctx.get_params(), O.flatten(theta))      # evaluation leaves theta alone
+    finally:
+        ctx.close()
+
+
+@pytest.mark.parametrize("shape", list(EVAL_SHAPES))
+def test_evaluation_behind_a_one_rank_communicator(shape):
+    """validate_resident and marginal_ll_resident all-reduce their sum over the ranks; with one
+    rank the share is every row and the sum is unchanged."""
+    from vaeb_amd import _lib
+    cfg, theta, _, _, x, eps, eps3, epsK = eval_inputs(shape)
+    ctx = context(cfg, theta, EVAL_MER)
+    try:
+        ctx.comm_init(_lib.Context.comm_unique_id(), 0, 1)
+        check_eval_calls(ctx, cfg, theta, None, x, eps, eps3, epsK, f"world 1 {shape}")
+    finally:
+        ctx.close()

@@ -315,3 +315,11 @@ def test_fp16_dp_path_world1_matches_fused_optimizer(overlap, fork, shard, monke
     assert abs(outs[0][0] - outs[1][0]) <= 1e-5 * abs(outs[0][0]), (outs[0][0], outs[1][0])
     assert np.abs(outs[0][1] - outs[1][1]).max() <= 1e-5
     assert rel(outs[1][2], outs[0][2]) <= 1e-4
+
+
+@pytest.mark.parametrize("gauss", [False, True])
+def test_fp16_resident_sampled_philox_and_refusals(gauss):
+    """(the sampled decoder means within the bf16 engine's 2e-2: this file has no sampled case)"""
+    from tests.test_gpu_bf16 import h16_resident_sampled_and_refusals
+    from vaeb_amd import _lib
+    h16_resident_sampled_and_refusals(_lib.DTYPE_F16, O.fp16_round, 2e-2, gauss)

@@ -14,7 +14,7 @@
 //   vaeb_ae_marginal_ll   ae_chunks: ae_encode (zero noise), per pass of sample planes ae_iw_sample_kernel |
 //                         ae_decode_hidden | ae_output(VALUE) | iw_lse_kernel, then ae_sum_to_host
 // vaeb_ae_create lays theta out (an AeLayer per layer and head); device memory is the context's:
-// ae_alloc / ae_grow register it, vaeb_ae_destroy frees the list.
+// vaeb_ae::mem (dev_owner.hpp) registers every buffer where it is allocated, vaeb_ae_destroy releases it.
 
 // One affine map of theta: W [K x N] at theta + oW, b [N] at theta + ob.
 struct AeLayer { int K, N; int64_t oW, ob; };
@@ -29,7 +29,7 @@ struct vaeb_ae {
     int64_t P = 0;
     AeLayer enc[VAEB_AE_MAX_LAYERS] = {}, dec[VAEB_AE_MAX_LAYERS] = {};   // Dobs -> Denc..., Dz -> Ddec...
     AeHeads lat{}, out{};             // d: dZ, or dmu and dlv (Gaussian latent); dA (and dA2, cont)
-    std::vector<void*> owned;         // every device allocation (ae_alloc / ae_grow); freed by vaeb_ae_destroy
+    DevOwner mem;                     // every device allocation; released by vaeb_ae_destroy
     float *theta = nullptr, *acc = nullptr;
     float* data = nullptr;
     int64_t nrows = 0;
@@ -62,41 +62,6 @@ struct vaeb_ae {
 
 namespace {
 
-// ------------------------------------------------------------------ device memory
-// n (at least one) zeroed elements, owned by the context from here on.
-template <class T>
-int ae_alloc(vaeb_ae* a, T** p, int64_t n) {
-    const int rc = dalloc(p, (size_t)std::max<int64_t>(n, 1));
-    if (*p) a->owned.push_back(*p);
-    return rc;
-}
-
-// A buffer that exists from its first use on.
-template <class T>
-int ae_lazy(vaeb_ae* a, T** p, int64_t n) { return *p ? 0 : ae_alloc(a, p, n); }
-
-// Replaces *p by a fresh buffer of n elements (contents are not kept).
-template <class T>
-int ae_realloc(vaeb_ae* a, T** p, int64_t n) {
-    auto it = std::find(a->owned.begin(), a->owned.end(), (void*)*p);
-    if (it != a->owned.end()) {
-        hipFree(*p);
-        a->owned.erase(it);
-    }
-    *p = nullptr;
-    return ae_alloc(a, p, n);
-}
-
-// A grow-only buffer: at least n elements.
-template <class T>
-int ae_grow(vaeb_ae* a, T** p, int64_t* cap, int64_t n) {
-    if (n <= *cap) return 0;
-    *cap = 0;
-    if (int rc = ae_realloc(a, p, n)) return rc;
-    *cap = n;
-    return 0;
-}
-
 bool ae_gauss(const vaeb_ae* a) { return a->c.latent == VAEB_AE_LATENT_GAUSS; }
 bool ae_act_latent(const vaeb_ae* a) { return a->c.latent == VAEB_AE_LATENT_ACT; }
 bool ae_iw(const vaeb_ae* a) { return a->c.iw_samples >= 2; }
@@ -104,13 +69,13 @@ bool ae_iw(const vaeb_ae* a) { return a->c.iw_samples >= 2; }
 // vaeb_ae_marginal_ll's and the importance-weighted step's scratch, sized by max_batch
 int ae_iw_scratch(vaeb_ae* a) {
     const int64_t B = a->c.max_batch;
-    if (int rc = ae_lazy(a, &a->iw, 4 * B)) return rc;
-    return ae_lazy(a, &a->iw_yrow, B);
+    if (int rc = a->mem.lazy(&a->iw, 4 * B)) return rc;
+    return a->mem.lazy(&a->iw_yrow, B);
 }
 
 int ae_reserve(vaeb_ae* a, int n_idx, int n_out) {
-    if (int rc = ae_grow(a, &a->idx, &a->idx_cap, n_idx)) return rc;
-    return ae_grow(a, &a->outs, &a->outs_cap, n_out);
+    if (int rc = a->mem.grow(&a->idx, &a->idx_cap, n_idx)) return rc;
+    return a->mem.grow(&a->outs, &a->outs_cap, n_out);
 }
 
 // ------------------------------------------------------------------ forward
@@ -473,31 +438,31 @@ int vaeb_ae_create(const vaeb_ae_config* cfg, vaeb_ae** out) {
     a->P = o;
     const int64_t B = g.max_batch;
     int rc = 0;
-    rc = rc ? rc : ae_alloc(a, &a->theta, a->P);
-    rc = rc ? rc : ae_alloc(a, &a->acc, a->P);
+    rc = rc ? rc : a->mem.alloc(&a->theta, a->P);
+    rc = rc ? rc : a->mem.alloc(&a->acc, a->P);
     for (int i = 1; i <= g.n_enc; ++i) {
-        rc = rc ? rc : ae_alloc(a, &a->H[i], B * a->enc[i - 1].N);
-        rc = rc ? rc : ae_alloc(a, &a->dH[i], B * a->enc[i - 1].N);
+        rc = rc ? rc : a->mem.alloc(&a->H[i], B * a->enc[i - 1].N);
+        rc = rc ? rc : a->mem.alloc(&a->dH[i], B * a->enc[i - 1].N);
     }
     for (int i = 1; i <= g.n_dec; ++i) {
-        rc = rc ? rc : ae_alloc(a, &a->G[i], B * a->dec[i - 1].N);
-        rc = rc ? rc : ae_alloc(a, &a->dG[i], B * a->dec[i - 1].N);
+        rc = rc ? rc : a->mem.alloc(&a->G[i], B * a->dec[i - 1].N);
+        rc = rc ? rc : a->mem.alloc(&a->dG[i], B * a->dec[i - 1].N);
     }
-    for (float** p : {&a->Z, &a->dZ}) rc = rc ? rc : ae_alloc(a, p, B * g.Dz);
+    for (float** p : {&a->Z, &a->dZ}) rc = rc ? rc : a->mem.alloc(p, B * g.Dz);
     // ls2 and dA2 on every output type
-    for (float** p : {&a->Xpr, &a->ls2, &a->dA, &a->dA2}) rc = rc ? rc : ae_alloc(a, p, B * g.Dobs);
-    rc = rc ? rc : ae_alloc(a, &a->ll, B * cdiv(g.Dobs, 16));
-    rc = rc ? rc : ae_alloc(a, &a->xin, B * std::max(g.Dobs, g.Dz));
+    for (float** p : {&a->Xpr, &a->ls2, &a->dA, &a->dA2}) rc = rc ? rc : a->mem.alloc(p, B * g.Dobs);
+    rc = rc ? rc : a->mem.alloc(&a->ll, B * cdiv(g.Dobs, 16));
+    rc = rc ? rc : a->mem.alloc(&a->xin, B * std::max(g.Dobs, g.Dz));
     if (ae_gauss(a)) {
-        for (float** p : {&a->mu, &a->lv, &a->dmu, &a->dlv}) rc = rc ? rc : ae_alloc(a, p, B * g.Dz);
-        rc = rc ? rc : ae_alloc(a, &a->kl, B * cdiv(g.Dz, 16));
-        rc = rc ? rc : ae_alloc(a, &a->esum, 1);
+        for (float** p : {&a->mu, &a->lv, &a->dmu, &a->dlv}) rc = rc ? rc : a->mem.alloc(p, B * g.Dz);
+        rc = rc ? rc : a->mem.alloc(&a->kl, B * cdiv(g.Dz, 16));
+        rc = rc ? rc : a->mem.alloc(&a->esum, 1);
     }
     if (ae_iw(a)) {
         rc = rc ? rc : ae_iw_scratch(a);
-        rc = rc ? rc : ae_alloc(a, &a->iw_wt, B);
-        rc = rc ? rc : ae_alloc(a, &a->iw_val, B);
-        rc = rc ? rc : ae_alloc(a, &a->iw_lw, B);
+        rc = rc ? rc : a->mem.alloc(&a->iw_wt, B);
+        rc = rc ? rc : a->mem.alloc(&a->iw_val, B);
+        rc = rc ? rc : a->mem.alloc(&a->iw_lw, B);
     }
     rc = rc ? rc : ae_reserve(a, (int)B, 1);
     a->out.d[0] = a->dA; a->out.d[1] = a->dA2;
@@ -511,7 +476,7 @@ int vaeb_ae_create(const vaeb_ae_config* cfg, vaeb_ae** out) {
 int vaeb_ae_destroy(vaeb_ae* a) {
     if (!a) return 0;
     if (a->s) hipStreamSynchronize(a->s);
-    for (void* p : a->owned) hipFree(p);
+    a->mem.release_all();
     if (a->s) hipStreamDestroy(a->s);
     delete a;
     return 0;
@@ -526,7 +491,7 @@ int vaeb_ae_num_params(const vaeb_ae* a, int64_t* n) {
 int vaeb_ae_set_data(vaeb_ae* a, const float* x, int64_t n_rows) {
     if (!a || !x || n_rows <= 0) return fail(VAEB_ERR_ARG, "bad data arguments");
     HIP_TRY(hipStreamSynchronize(a->s));
-    if (int rc = ae_realloc(a, &a->data, n_rows * a->c.Dobs)) return rc;
+    if (int rc = a->mem.replace(&a->data, n_rows * a->c.Dobs)) return rc;
     HIP_TRY(hipMemcpy(a->data, x, sizeof(float) * (size_t)n_rows * a->c.Dobs, hipMemcpyHostToDevice));
     a->nrows = n_rows;
     return 0;
@@ -571,8 +536,8 @@ int vaeb_ae_decode(vaeb_ae* a, const float* z, int64_t n, float* out) { return a
 int vaeb_ae_sq_error(vaeb_ae* a, const float* x, int64_t n, double* out_sum, float* out_rows) {
     if (!a || !x || !out_sum || n <= 0) return fail(VAEB_ERR_ARG, "bad arguments");
     const vaeb_ae_config& g = a->c;
-    if (int rc = ae_lazy(a, &a->sq_rows, g.max_batch)) return rc;
-    if (int rc = ae_lazy(a, &a->esum, 1)) return rc;
+    if (int rc = a->mem.lazy(&a->sq_rows, g.max_batch)) return rc;
+    if (int rc = a->mem.lazy(&a->esum, 1)) return rc;
     double total = 0.0;
     if (int rc = ae_chunks(a, x, n, g.Dobs, [&](int64_t r0, int rows) {
             // the deterministic forward (Gaussian latent: z = mu), then the mean head's (Y - P)^2 partials
@@ -611,7 +576,7 @@ int vaeb_ae_push_eps(vaeb_ae* a, const float* eps, int64_t rows) {
     const int64_t n = rows * a->c.Dz;
     HIP_TRY(hipStreamSynchronize(a->s));
     if (n > a->eps_cap) a->eps_rows = 0;   // the old rows go with the old buffer
-    if (int rc = ae_grow(a, &a->eps_in, &a->eps_cap, n)) return rc;
+    if (int rc = a->mem.grow(&a->eps_in, &a->eps_cap, n)) return rc;
     HIP_TRY(hipMemcpy(a->eps_in, eps, sizeof(float) * (size_t)n, hipMemcpyHostToDevice));
     a->eps_rows = rows;
     return 0;

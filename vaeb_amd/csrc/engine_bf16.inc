@@ -13,10 +13,10 @@
 //   bf_train_step bf_step_form -> bf_forward -> dhd (| dW26 in its grid) -> dz -> [fork: dW26] dW1
 //                 (bf_wgrad_slabs) -> bf_latent_bwd | thin dz -> dh -> dW45 (bf_wgrad_slabs) -> dW3 ->
 //                 bias + ELBO, its partial rows from bf_partial_rows of the forms the plan recorded
-//   evaluation    bf_eval_chunk -> bf_eval_chunk_dev -> bf_forward on bf_eval_fwd (vaeb_hip.hip)
-//   memory        bf_alloc registers every buffer in BfState::owned, bf_free walks it; the dataset
-//                 copies x, xbits and xval are replaced by vaeb_set_data / vaeb_set_valid_data, which
-//                 free them explicitly, as bf_free does at the end
+//   evaluation    eval_chunks (vaeb_hip.hip: stages host rows with bf_upload_rows) -> bf_eval_chunk_dev ->
+//                 bf_forward on bf_eval_fwd (vaeb_hip.hip)
+//   memory        BfState::mem (dev_owner.hpp) owns every buffer: bf_alloc's, and the dataset copies
+//                 x, xbits and xval that vaeb_set_data / vaeb_set_valid_data replace; bf_free releases it
 
 using bf::bf16_t;
 
@@ -223,14 +223,6 @@ BfStepForm bf_step_form(const vaeb_ctx* c, bool prof) {
 }
 
 // ---------------------------------------------------------------- memory
-// n zeroed elements, owned by the 16-bit state from here on (bf_free).
-template <class T>
-int bf_own(bf::BfState& b, T** p, size_t n) {
-    const int rc = dalloc(p, n);
-    if (*p) b.owned.push_back(*p);
-    return rc;
-}
-
 int bf_alloc(vaeb_ctx* c) {
     bf::BfState& b = c->bf;
     const vaeb_config& g = c->c;
@@ -266,7 +258,7 @@ int bf_alloc(vaeb_ctx* c) {
     b.thin_z = thin_ok && (c->bf_thin & 2);
     b.nkl = b.thin_h ? Z / 64 : 1;
     int rc = 0;
-    auto own = [&](auto** p, size_t n) { rc = rc ? rc : bf_own(b, p, n); };
+    auto own = [&](auto** p, size_t n) { rc = rc ? rc : b.mem.alloc(p, (int64_t)n); };
     own(&b.shadow2[0], (size_t)b.S);
     own(&b.shadow2[1], (size_t)b.S);
     own(&b.xeval, (size_t)R * D);
@@ -295,8 +287,7 @@ int bf_alloc(vaeb_ctx* c) {
 
 void bf_free(vaeb_ctx* c) {
     bf::BfState& b = c->bf;
-    for (void* p : b.owned) hipFree(p);
-    for (void* p : {(void*)b.x, (void*)b.xbits, (void*)b.xval}) if (p) hipFree(p);   // (vaeb_set_data / vaeb_set_valid_data)
+    b.mem.release_all();
     b = bf::BfState{};
 }
 
@@ -707,12 +698,6 @@ int bf_eval_chunk_dev(vaeb_ctx* c, const bf16_t* x, int rows, int64_t r0, int mo
         CHECK_LAUNCH();
     }
     return 0;
-}
-
-// ... of host fp32 rows (uploaded through the eval staging buffers).
-int bf_eval_chunk(vaeb_ctx* c, const float* x, int rows, int64_t r0, int mode, float* out_y) {
-    if (int rc = bf_upload_rows(c, x, rows, c->bf.xeval)) return rc;
-    return bf_eval_chunk_dev(c, c->bf.xeval, rows, r0, mode, out_y);
 }
 
 #include "h16_gemm_hooks.inc"   // vaeb_test_gemm_bf16 / vaeb_bench_gemm_bf16

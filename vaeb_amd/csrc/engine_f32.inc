@@ -773,6 +773,41 @@ int eval_chunk_f32(vaeb_ctx* c, int epar, const float* x, int rows, int64_t r0, 
     return 0;
 }
 
+// One posterior draw of one fp32 chunk (vaeb_reconstruct_full, n_samples > 0): the decoder outputs
+// at z = mu + exp(lv / 2) eps in c->y (| c->dA6), one plane.  eps: the Philox stream of `domain`
+// (sample s: 1 | (s + 1) << 1), or in host eps mode the pushed rows from eps_in (the sample's row
+// r0; null when nothing was pushed).
+int sample_chunk_f32(vaeb_ctx* c, int epar, const float* x, int rows, int64_t r0, uint32_t domain, const float* eps_in) {
+    StepArgs a = make_args(c, epar, rows, MODE_RECON, x, false);
+    a.L = 1; a.Me = a.Mbp;
+    a.eps_mode = c->eps_mode == VAEB_EPS_HOST ? 1 : 0;
+    a.domain = domain;
+    a.row_base_add = r0;
+    a.eps_in = eps_in; a.eps_in_ld = c->eps_rows;
+    Prof pr{c, false};
+    return enqueue_forward(c, a, pr);
+}
+
+// The decoder of one fp32 chunk at the caller's latents (vaeb_decode): `rows` host rows z [rows x Z]
+// staged into c->z, then hd, the means to out_mu and (Gaussian decoder, when asked for) the
+// log-sigma head to out_lv (host).
+int decode_chunk_f32(vaeb_ctx* c, int epar, const float* z, int rows, float* out_mu, float* out_lv) {
+    const vaeb_config& g = c->c;
+    StepArgs a = make_args(c, epar, rows, MODE_RECON, c->xeval, false);
+    a.L = 1; a.Me = a.Mbp;
+    // z rows, pad rows zero (PDecHid writes hd = 0 there)
+    HIP_TRY(hipMemsetAsync(c->z, 0, sizeof(float) * (size_t)a.Mbp * g.Z, c->s));
+    HIP_TRY(hipMemcpyAsync(c->z, z, sizeof(float) * (size_t)rows * g.Z, hipMemcpyHostToDevice, c->s));
+    launch_tile<1, 4, 1, 1, 8>(c->s, PDecHid{a, a.Me, a.H, a.Z});
+    CHECK_LAUNCH();
+    if (gaussian(c)) launch_bigk<2>(c->s, PDecOut{a, nullptr, a.Me, a.D, a.H});
+    else launch_bigk<1>(c->s, PDecOut{a, nullptr, a.Me, a.D, a.H});
+    CHECK_LAUNCH();
+    HIP_TRY(hipMemcpyAsync(out_mu, c->y, sizeof(float) * (size_t)rows * g.D, hipMemcpyDeviceToHost, c->s));
+    if (out_lv) HIP_TRY(hipMemcpyAsync(out_lv, c->dA6, sizeof(float) * (size_t)rows * g.D, hipMemcpyDeviceToHost, c->s));
+    return 0;
+}
+
 // The encoder and heads of one fp32 chunk (rows at x = global rows [r0, r0 + rows)): c->mu and
 // c->lv hold it afterwards (VAEB.py:245-251).  The forward's own launches with zero noise and
 // one plane; what they also write (eps, z, hd plane 0, the KL partials) is scratch here.

@@ -4,6 +4,7 @@
 #pragma once
 #include <vector>
 
+#include "dev_owner.hpp"
 #include "tile_engine.hpp"
 
 namespace vaeb {
@@ -64,7 +65,7 @@ struct BfState {
     bool thin_h = false, thin_z = false;   // heads / dz on the thin launches
     int nkl = 1;
     ShadowMap smap{};
-    std::vector<void*> owned;          // host: the engine's device allocations (bf_alloc; freed by bf_free)
+    DevOwner mem;                      // host: the engine's device allocations (bf_alloc, the dataset copies; bf_free)
 };
 
 }  // namespace h16c

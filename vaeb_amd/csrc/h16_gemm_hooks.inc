@@ -32,18 +32,19 @@ int h16_test_gemm(vaeb_ctx* c, int32_t ako, int32_t bko, int32_t M, int32_t N, i
     const int nz = bf_slices(K, ksplit);
     float *fa = nullptr, *fb = nullptr, *fc = nullptr;
     bf16_t *ba = nullptr, *bb = nullptr;
+    DevScratch tmp;   // freed on every return
     int rc = 0;
-    rc = rc ? rc : dalloc(&fa, na);
-    rc = rc ? rc : dalloc(&fb, nb);
-    rc = rc ? rc : dalloc(&ba, na);
-    rc = rc ? rc : dalloc(&bb, nb);
-    rc = rc ? rc : dalloc(&fc, (size_t)nz * M * N);
+    rc = rc ? rc : tmp.alloc(&fa, na);
+    rc = rc ? rc : tmp.alloc(&fb, nb);
+    rc = rc ? rc : tmp.alloc(&ba, na);
+    rc = rc ? rc : tmp.alloc(&bb, nb);
+    rc = rc ? rc : tmp.alloc(&fc, (int64_t)nz * M * N);
     float* part = nullptr;
     int* ticket = nullptr;
     const int tiles256 = cdiv(M, bf::BM) * cdiv(N, 256);
     if (split2) {
-        rc = rc ? rc : dalloc(&part, (size_t)tiles256 * 65536);
-        rc = rc ? rc : dalloc(&ticket, (size_t)tiles256);
+        rc = rc ? rc : tmp.alloc(&part, (int64_t)tiles256 * 65536);
+        rc = rc ? rc : tmp.alloc(&ticket, tiles256);
     }
     if (!rc) {
         hipMemcpy(fa, A, na * 4, hipMemcpyHostToDevice);
@@ -80,7 +81,6 @@ int h16_test_gemm(vaeb_ctx* c, int32_t ako, int32_t bko, int32_t M, int32_t N, i
             rc = fail(VAEB_ERR_HIP, "test gemm: ticket copy");
         for (int t : tk) if (!rc && t != 0) rc = fail(VAEB_ERR_HIP, "test gemm: split-K ticket left at %d", t);
     }
-    for (void* p : {(void*)fa, (void*)fb, (void*)fc, (void*)ba, (void*)bb, (void*)part, (void*)ticket}) if (p) hipFree(p);
     return rc;
 }
 
@@ -119,16 +119,17 @@ int h16_bench_gemm(vaeb_ctx* c, int32_t ako, int32_t bko, int32_t M, int32_t N, 
     bf16_t *a = nullptr, *b = nullptr, *o = nullptr;
     float *bias = nullptr, *part = nullptr;
     int* ticket = nullptr;
+    DevScratch tmp;   // freed on every return
     int rc = 0;
     if (bn == 9) {
         const int tiles = cdiv(M, bf::BM) * cdiv(N, 256);
-        rc = rc ? rc : dalloc(&part, (size_t)tiles * 65536);
-        rc = rc ? rc : dalloc(&ticket, (size_t)tiles);
+        rc = rc ? rc : tmp.alloc(&part, (int64_t)tiles * 65536);
+        rc = rc ? rc : tmp.alloc(&ticket, tiles);
     }
-    rc = rc ? rc : dalloc(&a, (size_t)M * K);
-    rc = rc ? rc : dalloc(&b, (size_t)N * K);
-    rc = rc ? rc : dalloc(&o, (size_t)M * N);
-    rc = rc ? rc : dalloc(&bias, (size_t)N);
+    rc = rc ? rc : tmp.alloc(&a, (int64_t)M * K);
+    rc = rc ? rc : tmp.alloc(&b, (int64_t)N * K);
+    rc = rc ? rc : tmp.alloc(&o, (int64_t)M * N);
+    rc = rc ? rc : tmp.alloc(&bias, N);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (!rc) {
         hipLaunchKernelGGL(fill_bf16_kernel, dim3(1024), dim3(256), 0, c->s, a, (int64_t)M * K, 1u);
@@ -155,6 +156,5 @@ int h16_bench_gemm(vaeb_ctx* c, int32_t ako, int32_t bko, int32_t M, int32_t N, 
     }
     if (e0) hipEventDestroy(e0);
     if (e1) hipEventDestroy(e1);
-    for (void* p : {(void*)a, (void*)b, (void*)o, (void*)bias, (void*)part, (void*)ticket}) if (p) hipFree(p);
     return rc;
 }

@@ -6,6 +6,23 @@
 // (th.shared x_train, VAEB.py:184), activation/delta buffers, and a small control
 // block (batch order, cursor, Philox step, ELBO accumulators) so a step needs no host
 // round trip and can be replayed as a hipGraph.
+//
+// Call map of the host layer (the engines' own maps: engine_f32.inc, engine_bf16.inc, engine_ae.inc):
+//   memory      every device buffer is allocated through a DevOwner (dev_owner.hpp) -- vaeb_ctx::mem,
+//               BfState::mem, vaeb_ae::mem -- and freed by its release_all (vaeb_destroy, bf_free,
+//               vaeb_ae_destroy); replaced buffers (data, xval, eps_in, bf.x | xbits | xval) go through
+//               drop / replace / grow, a call's scratch through a DevScratch guard.  No hipFree elsewhere.
+//   training    vaeb_update -> step_eager;  vaeb_update_many -> [eager first step + order_hook] run_steps
+//               (graph replay, or eager) -> enqueue_train_step -> the context's engine.  reset_graphs
+//               wherever a captured value or address changes.
+//   evaluation  [refusals] -> eval_begin (arena) -> eval_chunks(source, body) -> one read-back:
+//     vaeb_validate, vaeb_reconstruct         eval_rows -> eval_pass: eval_chunk_f32 | bf_eval_chunk_dev
+//     vaeb_validate_resident                  eval_pass on the resident share -> eval_finish (all-reduce)
+//     vaeb_reconstruct_sampled / _full        per chunk and sample sample_chunk_f32 | bf_forward(bf_eval_fwd),
+//                                             recon_accum_kernel; copy out and synchronise per chunk
+//     vaeb_decode                             decode_chunk_f32 (stages z itself); one synchronise
+//     vaeb_encode                             encode_chunk_f32; one synchronise
+//     vaeb_marginal_ll(_resident)             iw_pass: iw_chunk_f32 -> eval_acc_read ([all-reduce,] synchronise)
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -131,9 +148,17 @@ struct ArenaSlots {
 
 }  // namespace
 
+// DevOwner's one allocation site (dev_owner.hpp): dalloc, registered once the memory exists.
+int vaeb::DevOwner::take(void** p, size_t bytes) {
+    const int rc = dalloc(reinterpret_cast<char**>(p), bytes);
+    if (*p) owned.push_back(*p);
+    return rc;
+}
+
 struct vaeb_ctx {
     vaeb_config c{};
     hipStream_t s = nullptr;   // every step launch goes to this one stream
+    DevOwner mem;              // every device buffer below (interior pointers excepted); vaeb_destroy releases it
     int64_t P = 0;
     int nparams = 0;
     int64_t off[12] = {};   // arena offsets, reference order
@@ -334,9 +359,6 @@ void bf_free(vaeb_ctx* c) { eng_bf::bf_free(c); }   // (type-independent: frees 
 int bf_make_shadow(vaeb_ctx* c, int par) { return H16_CALL(bf_make_shadow, c, par); }
 int bf_upload_rows(vaeb_ctx* c, const float* x, int64_t n, bf16_t* dst) { return H16_CALL(bf_upload_rows, c, x, n, dst); }
 int bf_forward(vaeb_ctx* c, int par, const BfFwd& f, Prof& pr) { return H16_CALL(bf_forward, c, par, f, pr); }
-int bf_eval_chunk(vaeb_ctx* c, const float* x, int rows, int64_t r0, int mode, float* out_y) {
-    return H16_CALL(bf_eval_chunk, c, x, rows, r0, mode, out_y);
-}
 int bf_eval_chunk_dev(vaeb_ctx* c, const bf16_t* x, int rows, int64_t r0, int mode, float* out_y) {
     return H16_CALL(bf_eval_chunk_dev, c, x, rows, r0, mode, out_y);
 }
@@ -357,6 +379,13 @@ void free_graphs(vaeb_ctx* c) {
             gn = nullptr;
         }
     c->w2_graph = false;
+}
+
+// What the captured steps hold by value or by address has changed: drop them, and let the next
+// call capture again (a capture that failed before may succeed now).
+void reset_graphs(vaeb_ctx* c) {
+    free_graphs(c);
+    c->graph_failed = false;
 }
 
 // Capture nsteps consecutive steps starting from parameter arena `par`.
@@ -472,6 +501,72 @@ int check_batches(vaeb_ctx* c, const int32_t* idx, int n) {
 }
 
 
+// ------------------------------------------------------------------ evaluation
+// Forward-only passes in chunks of max_eval_rows device rows.  Every call below is
+//   [refusals] -> eval_begin (the arena to read) -> eval_chunks(source, body) -> its one read-back,
+// and a body hands the chunk to the engine that owns its rows (engine_f32.inc *_chunk_f32,
+// engine_bf16.inc bf_eval_chunk_dev / bf_forward): no launch argument is filled here.
+
+// The arena an evaluation reads.  fp32: a pending deferred dW2 flushed first, then the current
+// theta, or for VAEB_EST_FVS the posterior mean mu_theta (copied into the spare arena once per
+// call).  16-bit: the current arena (no deferred dW2, no FV estimators there).
+int eval_begin(vaeb_ctx* c, int* epar) {
+    *epar = c->par;
+    if (is_bf16(c)) return 0;
+    if (int rc = w2_flush(c)) return rc;
+    if (c->c.estimator == VAEB_EST_FVS) {
+        *epar = c->par ^ 1;
+        HIP_TRY(hipMemcpyAsync(c->theta2[*epar], c->fvmu, sizeof(float) * (size_t)c->P, hipMemcpyDeviceToDevice, c->s));
+    }
+    return 0;
+}
+
+// The calls the 16-bit engine does not serve.
+int fp32_only(const vaeb_ctx* c, const char* what) {
+    return is_bf16(c) ? fail(VAEB_ERR_ARG, "%s is served by fp32 contexts", what) : 0;
+}
+
+// This rank's contiguous share of the resident rows: the first (n % world) ranks take one
+// extra row (the row split of vaeb_amd/dp.py).
+void valid_share(const vaeb_ctx* c, int64_t* lo, int64_t* rows) {
+    const int64_t W = c->comm ? c->world : 1, r = c->comm ? c->rank : 0;
+    const int64_t base = c->nval / W, extra = c->nval % W;
+    *rows = base + (r < extra ? 1 : 0);
+    *lo = r * base + std::min<int64_t>(r, extra);
+}
+
+// The rows a call walks: host rows x [n x D], staged chunk by chunk through the engine's eval
+// buffer; this rank's share of the n = nval resident rows; or (vaeb_decode) n rows that are no
+// observations, which the body stages itself.
+struct EvalSrc { const float* x; int64_t n; bool resident; };
+// One chunk's device rows in the context's engine type (the other pointer is null).
+struct EvalRows { const float* f32; const bf16_t* h16; };
+
+// The one chunk loop: body(device rows, rows, r0) for every chunk of at most max_eval_rows rows,
+// r0 the chunk's first global row (noise keys, host eps rows, output offsets).  Everything is
+// enqueued on the context stream; the synchronises are the caller's.
+template <class Body>
+int eval_chunks(vaeb_ctx* c, const EvalSrc& src, Body body) {
+    const int64_t D = c->c.D, chunk = c->c.max_eval_rows;
+    int64_t lo = 0, n = src.n;
+    if (src.resident) valid_share(c, &lo, &n);
+    for (int64_t r0 = lo; r0 < lo + n; r0 += chunk) {
+        const int rows = (int)std::min<int64_t>(chunk, lo + n - r0);
+        EvalRows d{};
+        if (src.resident) {
+            if (is_bf16(c)) d.h16 = c->bf.xval + r0 * D; else d.f32 = c->xval + r0 * D;
+        } else if (src.x && is_bf16(c)) {
+            if (int rc = bf_upload_rows(c, src.x + r0 * D, rows, c->bf.xeval)) return rc;
+            d.h16 = c->bf.xeval;
+        } else if (src.x) {
+            HIP_TRY(hipMemcpyAsync(c->xeval, src.x + r0 * D, sizeof(float) * (size_t)rows * D, hipMemcpyHostToDevice, c->s));
+            d.f32 = c->xeval;
+        }
+        if (int rc = body(d, rows, r0)) return rc;
+    }
+    return 0;
+}
+
 }  // namespace
 
 // =========================================================================== C ABI
@@ -540,50 +635,48 @@ int vaeb_create(const vaeb_config* cfg, vaeb_ctx** out) {
     c->cap = std::max(r16(g.B), r16(c->c.max_eval_rows));
     const int64_t R = c->cap, RL = (int64_t)c->cap * g.L;
     int rc = 0;
-    rc = rc ? rc : dalloc(&c->theta2[0], c->P);
-    rc = rc ? rc : dalloc(&c->theta2[1], c->P);
-    rc = rc ? rc : dalloc(&c->acc, c->P);
-    rc = rc ? rc : dalloc(&c->grad, c->P + 1);
-    if (g.estimator == VAEB_EST_FV || g.estimator == VAEB_EST_FVS) {
-        rc = rc ? rc : dalloc(&c->fvmu, c->P);
-        rc = rc ? rc : dalloc(&c->fvsg, c->P);
-        rc = rc ? rc : dalloc(&c->fvam, c->P);
-        rc = rc ? rc : dalloc(&c->fvas, c->P);
-    }
-    rc = rc ? rc : dalloc(&c->fv_part, kFvParts);
-    rc = rc ? rc : dalloc(&c->xeval, (size_t)R * D);
-    rc = rc ? rc : dalloc(&c->ictl, kCtlOrder + kOrderCap);
-    rc = rc ? rc : dalloc(&c->step, 1);
-    rc = rc ? rc : dalloc(&c->eval_acc, 2);
-    rc = rc ? rc : dalloc(&c->h, (size_t)R * H);
-    rc = rc ? rc : dalloc(&c->mu, (size_t)R * Z);
-    rc = rc ? rc : dalloc(&c->lv, (size_t)R * Z);
-    rc = rc ? rc : dalloc(&c->eps, (size_t)RL * Z);
-    rc = rc ? rc : dalloc(&c->z, (size_t)RL * Z);
-    rc = rc ? rc : dalloc(&c->hd, (size_t)RL * H);
-    rc = rc ? rc : dalloc(&c->y, (size_t)RL * D);
+    // every device buffer is registered with c->mem here, where it is allocated (vaeb_destroy releases the list)
+    auto own = [&](auto** p, int64_t n) { rc = rc ? rc : c->mem.alloc(p, n); };
+    own(&c->theta2[0], c->P);
+    own(&c->theta2[1], c->P);
+    own(&c->acc, c->P);
+    own(&c->grad, c->P + 1);
+    if (fvx)
+        for (float** p : {&c->fvmu, &c->fvsg, &c->fvam, &c->fvas}) own(p, c->P);
+    own(&c->fv_part, kFvParts);
+    own(&c->xeval, R * D);
+    own(&c->ictl, kCtlOrder + kOrderCap);
+    own(&c->step, 1);
+    own(&c->eval_acc, 2);
+    own(&c->h, R * H);
+    own(&c->mu, R * Z);
+    own(&c->lv, R * Z);
+    own(&c->eps, RL * Z);
+    own(&c->z, RL * Z);
+    own(&c->hd, RL * H);
+    own(&c->y, RL * D);
     // dA6 directly after dA2: the dhd loaders address both through one descriptor (PDhdT)
-    rc = rc ? rc : dalloc(&c->dA2, (size_t)RL * D * (gaussian(c) ? 2 : 1));
-    if (!rc && gaussian(c)) c->dA6 = c->dA2 + (size_t)RL * D;
-    rc = rc ? rc : dalloc(&c->dA1, (size_t)RL * H);
-    rc = rc ? rc : dalloc(&c->dZ, (size_t)RL * Z);
-    rc = rc ? rc : dalloc(&c->dMuLv, (size_t)R * 2 * Z);
-    rc = rc ? rc : dalloc(&c->dA3, (size_t)R * H);
-    rc = rc ? rc : dalloc(&c->kl_part, (size_t)RL * cdiv(Z, 16));
-    rc = rc ? rc : dalloc(&c->lp_part, (size_t)RL * cdiv(D, 16));
+    own(&c->dA2, RL * D * (gaussian(c) ? 2 : 1));
+    if (!rc && gaussian(c)) c->dA6 = c->dA2 + (size_t)RL * D;   // interior pointer: not registered
+    own(&c->dA1, RL * H);
+    own(&c->dZ, RL * Z);
+    own(&c->dMuLv, R * 2 * Z);
+    own(&c->dA3, R * H);
+    own(&c->kl_part, RL * cdiv(Z, 16));
+    own(&c->lp_part, RL * cdiv(D, 16));
     {   // folded-latent slabs and arrival counters (training minibatch only)
         const int64_t Bp = r16(g.B), nctH = cdiv(H, 16);
-        rc = rc ? rc : dalloc(&c->slab_ml, (size_t)(Bp * nctH * 64));
-        rc = rc ? rc : dalloc(&c->slab_dz, (size_t)(g.L * Bp * nctH * 32));
-        rc = rc ? rc : dalloc(&c->cnt_ml, (size_t)(Bp / 16));
-        rc = rc ? rc : dalloc(&c->cnt_dz, (size_t)std::max<int64_t>(Bp / 16, kLatCnt * kLatCntStride));
-        rc = rc ? rc : dalloc(&c->w2pend, 1);
+        own(&c->slab_ml, Bp * nctH * 64);
+        own(&c->slab_dz, g.L * Bp * nctH * 32);
+        own(&c->cnt_ml, Bp / 16);
+        own(&c->cnt_dz, std::max<int64_t>(Bp / 16, kLatCnt * kLatCntStride));
+        own(&c->w2pend, 1);
         // one allocation: the guard word the contributors set sits at acc_ml[-1] (latent.hpp fx_inc)
-        const size_t nacc = (size_t)(Bp * 2 * Z * kFxStride);
-        rc = rc ? rc : dalloc(&c->blk, kBlkAcc + 2 * nacc);
-        if (!rc) {
+        const int64_t nacc = Bp * 2 * Z * kFxStride;
+        own(&c->blk, kBlkAcc + 2 * nacc);
+        if (!rc) {   // interior pointers into blk: not registered (the step's result slot blk[kBlkElbo]
+                     // is unused: elbo_out is the mapped host slot below)
             c->epoch = reinterpret_cast<double*>(c->blk);
-            c->elbo_out = reinterpret_cast<float*>(c->blk + kBlkElbo);
             c->acc_ml = c->blk + kBlkAcc;
             c->acc_dz = c->acc_ml + nacc;
         }
@@ -631,17 +724,7 @@ int vaeb_destroy(vaeb_ctx* c) {
     free_graphs(c);
     bf_free(c);
     if (c->comm) ncclCommDestroy(c->comm);
-    float* fp[] = {c->theta2[0], c->theta2[1], c->acc, c->grad, c->fvmu, c->fvsg, c->fvam, c->fvas, c->fv_part, c->data, c->xeval, c->xval,
-                   c->eps_in, c->h, c->mu, c->lv, c->eps, c->z, c->hd, c->y, c->dA2, c->dA1,   // dA6 lives in dA2's block
-                   c->dZ, c->dMuLv, c->dA3, c->kl_part, c->lp_part, c->slab_ml, c->slab_dz, c->yacc,
-                   c->fvzeta, c->iw};
-    for (float* p : fp) if (p) hipFree(p);
-    if (c->cnt_ml) hipFree(c->cnt_ml);
-    if (c->cnt_dz) hipFree(c->cnt_dz);
-    if (c->blk) hipFree(c->blk);   // epoch, elbo_out, acc_ml, acc_dz live in it
-    if (c->ictl) hipFree(c->ictl);
-    if (c->step) hipFree(c->step);
-    if (c->eval_acc) hipFree(c->eval_acc);
+    c->mem.release_all();
     if (c->h_ctl) hipHostFree(c->h_ctl);
     if (c->h_elbo) hipHostFree(c->h_elbo);
     if (c->h_out) hipHostFree(c->h_out);
@@ -666,13 +749,12 @@ int vaeb_num_params(const vaeb_ctx* c, int64_t* n) {
 int vaeb_set_data(vaeb_ctx* c, const float* x, int64_t n_rows) {
     if (!c || !x || n_rows <= 0) return fail(VAEB_ERR_ARG, "bad data arguments");
     HIP_TRY(hipStreamSynchronize(c->s));
-    if (c->data) { hipFree(c->data); c->data = nullptr; }
-    free_graphs(c);  // graphs hold the data pointer
-    c->graph_failed = false;
+    c->mem.drop(&c->data);
+    reset_graphs(c);  // graphs hold the data pointer
     if (is_bf16(c)) {
         // the bf16 engine keeps only a bf16 copy; c->data stays a 16-byte placeholder
-        if (c->bf.x) { hipFree(c->bf.x); c->bf.x = nullptr; }
-        if (c->bf.xbits) { hipFree(c->bf.xbits); c->bf.xbits = nullptr; }
+        c->bf.mem.drop(&c->bf.x);
+        c->bf.mem.drop(&c->bf.xbits);
         // a binary dataset (every value exactly 0 or 1) also as bits, for the Bernoulli decoder
         // epilogue's x tile (EpiDecOutT::load_in): 1/16 of its bytes, the same values
         const int64_t D = c->c.D, nel = n_rows * D;
@@ -682,17 +764,17 @@ int vaeb_set_data(vaeb_ctx* c, const float* x, int64_t n_rows) {
             std::vector<uint32_t> bits((size_t)(nel / 32), 0u);
             for (int64_t i = 0; i < nel; ++i)
                 if (x[i] != 0.f) bits[(size_t)(i >> 5)] |= 1u << (i & 31);
-            if (int rc = dalloc(&c->bf.xbits, bits.size())) return rc;
+            if (int rc = c->bf.mem.alloc(&c->bf.xbits, (int64_t)bits.size())) return rc;
             HIP_TRY(hipMemcpy(c->bf.xbits, bits.data(), sizeof(uint32_t) * bits.size(), hipMemcpyHostToDevice));
         }
-        if (int rc = dalloc(&c->bf.x, (size_t)n_rows * c->c.D)) return rc;
-        if (int rc = dalloc(&c->data, 4)) return rc;
+        if (int rc = c->bf.mem.alloc(&c->bf.x, n_rows * c->c.D)) return rc;
+        if (int rc = c->mem.alloc(&c->data, 4)) return rc;
         if (int rc = bf_upload_rows(c, x, n_rows, c->bf.x)) return rc;
         HIP_TRY(hipStreamSynchronize(c->s));
         c->nrows = n_rows;
         return 0;
     }
-    if (int rc = dalloc(&c->data, (size_t)n_rows * c->c.D)) return rc;
+    if (int rc = c->mem.alloc(&c->data, n_rows * c->c.D)) return rc;
     HIP_TRY(hipMemcpy(c->data, x, sizeof(float) * (size_t)n_rows * c->c.D, hipMemcpyHostToDevice));
     c->nrows = n_rows;
     return 0;
@@ -747,7 +829,7 @@ int vaeb_set_eps_mode(vaeb_ctx* c, int32_t mode, uint64_t seed) {
     if (!c || (mode != VAEB_EPS_PHILOX && mode != VAEB_EPS_HOST)) return fail(VAEB_ERR_ARG, "bad eps mode");
     HIP_TRY(hipStreamSynchronize(c->s));
     // captured steps hold the eps mode's kernels and the Philox seed by value (make_args)
-    if (mode != c->eps_mode || seed != c->seed) { free_graphs(c); c->graph_failed = false; }
+    if (mode != c->eps_mode || seed != c->seed) reset_graphs(c);
     c->eps_mode = mode;
     c->seed = seed;
     return 0;
@@ -758,15 +840,9 @@ int vaeb_push_eps(vaeb_ctx* c, const float* eps, int64_t rows, int32_t L) {
     if (L != c->c.L) return fail(VAEB_ERR_ARG, "eps L=%d does not match the model L=%d", L, c->c.L);
     const int64_t n = rows * L * c->c.Z;
     HIP_TRY(hipStreamSynchronize(c->s));
-    if (n > c->eps_in_cap) {
-        if (c->eps_in) hipFree(c->eps_in);
-        c->eps_in = nullptr;
-        free_graphs(c);
-        c->graph_failed = false;
-        if (int rc = dalloc(&c->eps_in, (size_t)n)) return rc;
-        c->eps_in_cap = n;
-    }
-    if (rows != c->eps_rows) { free_graphs(c); c->graph_failed = false; }
+    // (captured steps hold the eps pointer and its row count)
+    if (n > c->eps_in_cap || rows != c->eps_rows) reset_graphs(c);
+    if (int rc = c->mem.grow(&c->eps_in, &c->eps_in_cap, n)) return rc;
     c->eps_rows = rows;
     HIP_TRY(hipMemcpy(c->eps_in, eps, sizeof(float) * n, hipMemcpyHostToDevice));
     return 0;
@@ -778,9 +854,8 @@ int vaeb_push_fv_noise(vaeb_ctx* c, const float* zeta, int64_t n) {
     if (n != c->P) return fail(VAEB_ERR_ARG, "weight noise needs %lld values (got %lld)", (long long)c->P, (long long)n);
     HIP_TRY(hipStreamSynchronize(c->s));
     if (!c->fvzeta) {
-        if (int rc = dalloc(&c->fvzeta, (size_t)c->P)) return rc;
-        free_graphs(c);   // captured steps hold the noise pointer
-        c->graph_failed = false;
+        if (int rc = c->mem.alloc(&c->fvzeta, c->P)) return rc;
+        reset_graphs(c);   // captured steps hold the noise pointer
     }
     HIP_TRY(hipMemcpy(c->fvzeta, zeta, sizeof(float) * (size_t)n, hipMemcpyHostToDevice));
     return 0;
@@ -923,19 +998,6 @@ int vaeb_synchronize(vaeb_ctx* c) {
     return 0;
 }
 
-// Forward-only passes in device chunks (validate / reconstruct).  The arena the data term
-// reads: the current theta, or for VAEB_EST_FVS the posterior mean mu_theta (copied into
-// the spare arena once per call).
-static int eval_arena(vaeb_ctx* c, int* epar) {
-    if (int rc = w2_flush(c)) return rc;
-    *epar = c->par;
-    if (c->c.estimator == VAEB_EST_FVS) {
-        *epar = c->par ^ 1;
-        HIP_TRY(hipMemcpyAsync(c->theta2[*epar], c->fvmu, sizeof(float) * (size_t)c->P, hipMemcpyDeviceToDevice, c->s));
-    }
-    return 0;
-}
-
 // eval_acc[0] on the host, after an optional all-reduce of it over the ranks: the call's
 // one stream synchronisation.
 static int eval_acc_read(vaeb_ctx* c, bool allreduce, double* out) {
@@ -971,32 +1033,32 @@ static int eval_finish(vaeb_ctx* c, int64_t n, bool allreduce, double* out_sum) 
     return 0;
 }
 
-// Host rows: each chunk is staged through xeval (stream-ordered, one sync at the end).
+// validate (MODE_EVAL: the chunks' SGVB summed in eval_acc) and reconstruct at z = mu (MODE_RECON:
+// the decoder means to out_y, the log-sigma head to out_lv) over src: stream-ordered, one
+// synchronise at the end.
+static int eval_pass(vaeb_ctx* c, const EvalSrc& src, int mode, float* out_y, double* out_sum, float* out_lv = nullptr) {
+    const int64_t D = c->c.D;
+    HIP_TRY(hipMemsetAsync(c->eval_acc, 0, 2 * sizeof(double), c->s));
+    int epar = 0;
+    if (int rc = eval_begin(c, &epar)) return rc;
+    if (int rc = eval_chunks(c, src, [&](EvalRows d, int rows, int64_t r0) {
+            float* yo = out_y ? out_y + r0 * D : nullptr;
+            return d.h16 ? bf_eval_chunk_dev(c, d.h16, rows, r0, mode, yo)
+                         : eval_chunk_f32(c, epar, d.f32, rows, r0, mode, yo, out_lv ? out_lv + r0 * D : nullptr);
+        }))
+        return rc;
+    if (mode == MODE_EVAL) return eval_finish(c, src.n, src.resident, out_sum);
+    HIP_TRY(hipStreamSynchronize(c->s));
+    return 0;
+}
+
 static int eval_rows(vaeb_ctx* c, const float* x, int64_t n, int mode, float* out_y, double* out_sum,
                      float* out_lv = nullptr) {
     if (!c || !x || n <= 0) return fail(VAEB_ERR_ARG, "bad arguments");
     if (mode == MODE_EVAL && c->eps_mode == VAEB_EPS_HOST && c->eps_rows != n)
         return fail(VAEB_ERR_STATE, "host eps mode: validate needs eps for %lld rows (pushed %lld)", (long long)n,
                     (long long)c->eps_rows);
-    const vaeb_config& g = c->c;
-    const int chunk = c->c.max_eval_rows;
-    HIP_TRY(hipMemsetAsync(c->eval_acc, 0, 2 * sizeof(double), c->s));
-    int epar = c->par;
-    if (!is_bf16(c)) if (int rc = eval_arena(c, &epar)) return rc;
-    for (int64_t r0 = 0; r0 < n; r0 += chunk) {
-        const int rows = (int)std::min<int64_t>(chunk, n - r0);
-        float* yo = out_y ? out_y + r0 * g.D : nullptr;
-        if (is_bf16(c)) {
-            if (int rc = bf_eval_chunk(c, x + r0 * g.D, rows, r0, mode, yo)) return rc;
-            continue;
-        }
-        HIP_TRY(hipMemcpyAsync(c->xeval, x + r0 * g.D, sizeof(float) * (size_t)rows * g.D, hipMemcpyHostToDevice, c->s));
-        if (int rc = eval_chunk_f32(c, epar, c->xeval, rows, r0, mode, yo, out_lv ? out_lv + r0 * g.D : nullptr))
-            return rc;
-    }
-    if (mode == MODE_EVAL) return eval_finish(c, n, false, out_sum);
-    HIP_TRY(hipStreamSynchronize(c->s));
-    return 0;
+    return eval_pass(c, EvalSrc{x, n, false}, mode, out_y, out_sum, out_lv);
 }
 
 int vaeb_validate(vaeb_ctx* c, const float* x, int64_t n, double* out_sum) {
@@ -1007,28 +1069,17 @@ int vaeb_validate(vaeb_ctx* c, const float* x, int64_t n, double* out_sum) {
 int vaeb_set_valid_data(vaeb_ctx* c, const float* x, int64_t n) {
     if (!c || !x || n <= 0) return fail(VAEB_ERR_ARG, "bad validation-set arguments");
     HIP_TRY(hipStreamSynchronize(c->s));
-    if (c->xval) { hipFree(c->xval); c->xval = nullptr; }
-    if (c->bf.xval) { hipFree(c->bf.xval); c->bf.xval = nullptr; }
     c->nval = 0;
     if (is_bf16(c)) {
-        if (int rc = dalloc(&c->bf.xval, (size_t)n * c->c.D)) return rc;
+        if (int rc = c->bf.mem.replace(&c->bf.xval, n * c->c.D)) return rc;
         if (int rc = bf_upload_rows(c, x, n, c->bf.xval)) return rc;
         HIP_TRY(hipStreamSynchronize(c->s));
     } else {
-        if (int rc = dalloc(&c->xval, (size_t)n * c->c.D)) return rc;
+        if (int rc = c->mem.replace(&c->xval, n * c->c.D)) return rc;
         HIP_TRY(hipMemcpy(c->xval, x, sizeof(float) * (size_t)n * c->c.D, hipMemcpyHostToDevice));
     }
     c->nval = n;
     return 0;
-}
-
-// This rank's contiguous share of the resident rows: the first (n % world) ranks take one
-// extra row (the row split of vaeb_amd/dp.py).
-static void valid_share(const vaeb_ctx* c, int64_t* lo, int64_t* rows) {
-    const int64_t W = c->comm ? c->world : 1, r = c->comm ? c->rank : 0;
-    const int64_t base = c->nval / W, extra = c->nval % W;
-    *rows = base + (r < extra ? 1 : 0);
-    *lo = r * base + std::min<int64_t>(r, extra);
 }
 
 int vaeb_validate_resident(vaeb_ctx* c, double* out_sum) {
@@ -1037,22 +1088,7 @@ int vaeb_validate_resident(vaeb_ctx* c, double* out_sum) {
     if (c->eps_mode == VAEB_EPS_HOST && c->eps_rows != c->nval)
         return fail(VAEB_ERR_STATE, "host eps mode: resident validation needs eps for all %lld rows (pushed %lld)",
                     (long long)c->nval, (long long)c->eps_rows);
-    const vaeb_config& g = c->c;
-    int64_t lo = 0, rows = 0;
-    valid_share(c, &lo, &rows);
-    HIP_TRY(hipMemsetAsync(c->eval_acc, 0, 2 * sizeof(double), c->s));
-    int epar = c->par;
-    if (!is_bf16(c)) if (int rc = eval_arena(c, &epar)) return rc;
-    const int chunk = g.max_eval_rows;
-    for (int64_t r0 = lo; r0 < lo + rows; r0 += chunk) {
-        const int m = (int)std::min<int64_t>(chunk, lo + rows - r0);
-        if (is_bf16(c)) {
-            if (int rc = bf_eval_chunk_dev(c, c->bf.xval + r0 * g.D, m, r0, MODE_EVAL, nullptr)) return rc;
-        } else {
-            if (int rc = eval_chunk_f32(c, epar, c->xval + r0 * g.D, m, r0, MODE_EVAL, nullptr)) return rc;
-        }
-    }
-    return eval_finish(c, c->nval, true, out_sum);
+    return eval_pass(c, EvalSrc{nullptr, c->nval, true}, MODE_EVAL, nullptr, out_sum);
 }
 
 int vaeb_get_step(vaeb_ctx* c, int64_t* step) {
@@ -1158,7 +1194,7 @@ int vaeb_checkpoint_load(vaeb_ctx* c, const char* path) {
     }
     HIP_TRY(hipMemcpy(c->step, &h.step, sizeof(int64_t), hipMemcpyHostToDevice));
     // captured steps hold the eps mode's kernels and the Philox seed by value (make_args)
-    if (h.eps_mode != c->eps_mode || h.seed != c->seed) { free_graphs(c); c->graph_failed = false; }
+    if (h.eps_mode != c->eps_mode || h.seed != c->seed) reset_graphs(c);
     c->eps_mode = h.eps_mode;
     c->seed = h.seed;
     return 0;
@@ -1181,44 +1217,28 @@ int vaeb_reconstruct_sampled(vaeb_ctx* c, const float* x, int64_t n, int32_t n_s
 int vaeb_reconstruct_full(vaeb_ctx* c, const float* x, int64_t n, int32_t n_samples, float* out_y, float* out_lv) {
     if (!c || !x || n <= 0 || !out_y) return fail(VAEB_ERR_ARG, "bad arguments");
     if (out_lv && !gaussian(c)) return fail(VAEB_ERR_ARG, "the log-sigma head exists for the Gaussian decoder only");
-    if (out_lv && is_bf16(c)) return fail(VAEB_ERR_ARG, "the log-sigma output is served by fp32 contexts");
+    if (out_lv) if (int rc = fp32_only(c, "the log-sigma output")) return rc;
     if (n_samples <= 0) return eval_rows(c, x, n, MODE_RECON, out_y, nullptr, out_lv);
     const bool host = c->eps_mode == VAEB_EPS_HOST;
     if (host && c->eps_rows != n * n_samples)
         return fail(VAEB_ERR_STATE, "host eps mode: sampled reconstruct needs eps for %lld rows (n * n_samples), pushed %lld",
                     (long long)(n * n_samples), (long long)c->eps_rows);
     const vaeb_config& g = c->c;
-    const int chunk = g.max_eval_rows;
-    if (!c->yacc) {
-        if (int rc = dalloc(&c->yacc, (size_t)chunk * g.D * (gaussian(c) ? 2 : 1))) return rc;
-    }
-    float* lacc = gaussian(c) ? c->yacc + (size_t)chunk * g.D : nullptr;
-    int epar = c->par;
-    if (!is_bf16(c)) if (int rc = eval_arena(c, &epar)) return rc;
-    for (int64_t r0 = 0; r0 < n; r0 += chunk) {
-        const int rows = (int)std::min<int64_t>(chunk, n - r0);
+    const int64_t nacc = (int64_t)g.max_eval_rows * g.D;
+    if (int rc = c->mem.lazy(&c->yacc, nacc * (gaussian(c) ? 2 : 1))) return rc;
+    float* lacc = gaussian(c) ? c->yacc + nacc : nullptr;   // (interior pointer)
+    int epar = 0;
+    if (int rc = eval_begin(c, &epar)) return rc;
+    // per chunk: the samples' decoder outputs summed in yacc (| lacc), copied out, one synchronise
+    return eval_chunks(c, EvalSrc{x, n, false}, [&](EvalRows d, int rows, int64_t r0) {
         const int64_t ny = (int64_t)rows * g.D;
-        if (is_bf16(c)) {
-            if (int rc = bf_upload_rows(c, x + r0 * g.D, rows, c->bf.xeval)) return rc;
-        } else {
-            HIP_TRY(hipMemcpyAsync(c->xeval, x + r0 * g.D, sizeof(float) * (size_t)ny, hipMemcpyHostToDevice, c->s));
-        }
         for (int sidx = 0; sidx < n_samples; ++sidx) {
             const uint32_t domain = 1u | ((uint32_t)(sidx + 1) << 1);
             const float* eps = (host && c->eps_in) ? c->eps_in + ((int64_t)sidx * n + r0) * g.Z : nullptr;
             Prof pr{c, false};
-            if (is_bf16(c)) {
-                const BfFwd f = bf_eval_fwd(c, c->bf.xeval, rows, r0, MODE_EVAL, eps, domain, c->y);
-                if (int rc = bf_forward(c, c->par, f, pr)) return rc;
-            } else {
-                StepArgs a = make_args(c, epar, rows, MODE_RECON, c->xeval, false);
-                a.L = 1; a.Me = a.Mbp;
-                a.eps_mode = host ? 1 : 0;
-                a.domain = domain;
-                a.row_base_add = r0;
-                a.eps_in = eps; a.eps_in_ld = c->eps_rows;
-                if (int rc = enqueue_forward(c, a, pr)) return rc;
-            }
+            if (int rc = d.h16 ? bf_forward(c, epar, bf_eval_fwd(c, d.h16, rows, r0, MODE_EVAL, eps, domain, c->y), pr)
+                               : sample_chunk_f32(c, epar, d.f32, rows, r0, domain, eps))
+                return rc;
             const float scale = (sidx == n_samples - 1) ? (float)n_samples : 0.f;
             const dim3 grid((unsigned)std::min<int64_t>(1024, cdiv(ny, 256)));
             hipLaunchKernelGGL(recon_accum_kernel, grid, dim3(256), 0, c->s, c->yacc, c->y, ny, sidx == 0 ? 1 : 0, scale);
@@ -1232,8 +1252,8 @@ int vaeb_reconstruct_full(vaeb_ctx* c, const float* x, int64_t n, int32_t n_samp
         if (out_lv)
             HIP_TRY(hipMemcpyAsync(out_lv + r0 * g.D, lacc, sizeof(float) * (size_t)ny, hipMemcpyDeviceToHost, c->s));
         HIP_TRY(hipStreamSynchronize(c->s));
-    }
-    return 0;
+        return 0;
+    });
 }
 
 // The decoder from a given z (freyFace.py:173-187 `image(z)`, compiled at :237-245; VAEB.py
@@ -1242,27 +1262,14 @@ int vaeb_reconstruct_full(vaeb_ctx* c, const float* x, int64_t n, int32_t n_samp
 int vaeb_decode(vaeb_ctx* c, const float* z, int64_t n, float* out_mu, float* out_lv) {
     if (!c || !z || n <= 0 || !out_mu) return fail(VAEB_ERR_ARG, "bad arguments");
     if (out_lv && !gaussian(c)) return fail(VAEB_ERR_ARG, "the log-sigma head exists for the Gaussian decoder only");
-    if (is_bf16(c)) return fail(VAEB_ERR_ARG, "vaeb_decode is served by fp32 contexts");
+    if (int rc = fp32_only(c, "vaeb_decode")) return rc;
     const vaeb_config& g = c->c;
-    const int chunk = g.max_eval_rows;
-    int epar = c->par;
-    if (int rc = eval_arena(c, &epar)) return rc;
-    for (int64_t r0 = 0; r0 < n; r0 += chunk) {
-        const int rows = (int)std::min<int64_t>(chunk, n - r0);
-        StepArgs a = make_args(c, epar, rows, MODE_RECON, c->xeval, false);
-        a.L = 1; a.Me = a.Mbp;
-        // z rows, pad rows zero (PDecHid writes hd = 0 there)
-        HIP_TRY(hipMemsetAsync(c->z, 0, sizeof(float) * (size_t)a.Mbp * g.Z, c->s));
-        HIP_TRY(hipMemcpyAsync(c->z, z + r0 * g.Z, sizeof(float) * (size_t)rows * g.Z, hipMemcpyHostToDevice, c->s));
-        launch_tile<1, 4, 1, 1, 8>(c->s, PDecHid{a, a.Me, a.H, a.Z});
-        CHECK_LAUNCH();
-        if (gaussian(c)) launch_bigk<2>(c->s, PDecOut{a, nullptr, a.Me, a.D, a.H});
-        else launch_bigk<1>(c->s, PDecOut{a, nullptr, a.Me, a.D, a.H});
-        CHECK_LAUNCH();
-        HIP_TRY(hipMemcpyAsync(out_mu + r0 * g.D, c->y, sizeof(float) * (size_t)rows * g.D, hipMemcpyDeviceToHost, c->s));
-        if (out_lv)
-            HIP_TRY(hipMemcpyAsync(out_lv + r0 * g.D, c->dA6, sizeof(float) * (size_t)rows * g.D, hipMemcpyDeviceToHost, c->s));
-    }
+    int epar = 0;
+    if (int rc = eval_begin(c, &epar)) return rc;
+    if (int rc = eval_chunks(c, EvalSrc{nullptr, n, false}, [&](EvalRows, int rows, int64_t r0) {
+            return decode_chunk_f32(c, epar, z + r0 * g.Z, rows, out_mu + r0 * g.D, out_lv ? out_lv + r0 * g.D : nullptr);
+        }))
+        return rc;
     HIP_TRY(hipStreamSynchronize(c->s));
     return 0;
 }
@@ -1270,72 +1277,54 @@ int vaeb_decode(vaeb_ctx* c, const float* z, int64_t n, float* out_mu, float* ou
 // ------------------------------------------------------------------ encoder outputs, IWAE bound
 int vaeb_encode(vaeb_ctx* c, const float* x, int64_t n, float* out_mu, float* out_lv) {
     if (!c || !x || n <= 0) return fail(VAEB_ERR_ARG, "bad arguments");
-    if (is_bf16(c)) return fail(VAEB_ERR_ARG, "vaeb_encode is served by fp32 contexts");
+    if (int rc = fp32_only(c, "vaeb_encode")) return rc;
     const vaeb_config& g = c->c;
-    const int chunk = g.max_eval_rows;
-    int epar = c->par;
-    if (int rc = eval_arena(c, &epar)) return rc;
-    for (int64_t r0 = 0; r0 < n; r0 += chunk) {
-        const int rows = (int)std::min<int64_t>(chunk, n - r0);
-        HIP_TRY(hipMemcpyAsync(c->xeval, x + r0 * g.D, sizeof(float) * (size_t)rows * g.D, hipMemcpyHostToDevice, c->s));
-        if (int rc = encode_chunk_f32(c, epar, c->xeval, rows, r0, nullptr)) return rc;
-        const size_t nb = sizeof(float) * (size_t)rows * g.Z;
-        if (out_mu) HIP_TRY(hipMemcpyAsync(out_mu + r0 * g.Z, c->mu, nb, hipMemcpyDeviceToHost, c->s));
-        if (out_lv) HIP_TRY(hipMemcpyAsync(out_lv + r0 * g.Z, c->lv, nb, hipMemcpyDeviceToHost, c->s));
-    }
+    int epar = 0;
+    if (int rc = eval_begin(c, &epar)) return rc;
+    if (int rc = eval_chunks(c, EvalSrc{x, n, false}, [&](EvalRows d, int rows, int64_t r0) {
+            if (int rc = encode_chunk_f32(c, epar, d.f32, rows, r0, nullptr)) return rc;
+            const size_t nb = sizeof(float) * (size_t)rows * g.Z;
+            if (out_mu) HIP_TRY(hipMemcpyAsync(out_mu + r0 * g.Z, c->mu, nb, hipMemcpyDeviceToHost, c->s));
+            if (out_lv) HIP_TRY(hipMemcpyAsync(out_lv + r0 * g.Z, c->lv, nb, hipMemcpyDeviceToHost, c->s));
+            return 0;
+        }))
+        return rc;
     HIP_TRY(hipStreamSynchronize(c->s));
     return 0;
 }
 
-// Argument / state checks shared by the two marginal-likelihood calls, and the lazily
-// allocated scratch; n: the rows the pushed eps must cover K times.
-static int iw_begin(vaeb_ctx* c, int64_t n, int32_t K, int* epar) {
-    if (is_bf16(c)) return fail(VAEB_ERR_ARG, "vaeb_marginal_ll is served by fp32 contexts");
+// The K-sample importance-weighted sum over src (fp32 contexts): argument / state checks, the
+// lazily allocated scratch, the chunks, and eval_acc read once at the end (resident rows:
+// all-reduced over the ranks).  The pushed eps must cover src.n rows K times.
+static int iw_pass(vaeb_ctx* c, const EvalSrc& src, int32_t K, double* out_sum, float* out_rows) {
     if (K < 1 || K > (1 << 20))
         return fail(VAEB_ERR_ARG, "K = %d: 1 to 2^20 samples (the Philox sample-stream field)", K);
-    if (c->eps_mode == VAEB_EPS_HOST && c->eps_rows != n * K)
+    if (c->eps_mode == VAEB_EPS_HOST && c->eps_rows != src.n * K)
         return fail(VAEB_ERR_STATE, "host eps mode: the marginal likelihood needs eps for %lld rows (n * K), pushed %lld",
-                    (long long)(n * K), (long long)c->eps_rows);
-    if (!c->iw) {
-        if (int rc = dalloc(&c->iw, (size_t)c->cap * (c->c.L + 3))) return rc;
-    }
+                    (long long)(src.n * K), (long long)c->eps_rows);
+    if (int rc = c->mem.lazy(&c->iw, (int64_t)c->cap * (c->c.L + 3))) return rc;
     HIP_TRY(hipMemsetAsync(c->eval_acc, 0, 2 * sizeof(double), c->s));
-    return eval_arena(c, epar);
+    int epar = 0;
+    if (int rc = eval_begin(c, &epar)) return rc;
+    if (int rc = eval_chunks(c, src, [&](EvalRows d, int rows, int64_t r0) {
+            return iw_chunk_f32(c, epar, d.f32, rows, r0, K, c->eps_in ? c->eps_in + r0 * c->c.Z : nullptr, src.n,
+                                out_rows ? out_rows + r0 : nullptr);
+        }))
+        return rc;
+    return eval_acc_read(c, src.resident, out_sum);
 }
 
 int vaeb_marginal_ll(vaeb_ctx* c, const float* x, int64_t n, int32_t K, double* out_sum, float* out_rows) {
     if (!c || !x || n <= 0 || !out_sum) return fail(VAEB_ERR_ARG, "bad arguments");
-    int epar = 0;
-    if (int rc = iw_begin(c, n, K, &epar)) return rc;
-    const vaeb_config& g = c->c;
-    const int chunk = g.max_eval_rows;
-    for (int64_t r0 = 0; r0 < n; r0 += chunk) {
-        const int rows = (int)std::min<int64_t>(chunk, n - r0);
-        HIP_TRY(hipMemcpyAsync(c->xeval, x + r0 * g.D, sizeof(float) * (size_t)rows * g.D, hipMemcpyHostToDevice, c->s));
-        if (int rc = iw_chunk_f32(c, epar, c->xeval, rows, r0, K, c->eps_in ? c->eps_in + r0 * g.Z : nullptr, n,
-                                  out_rows ? out_rows + r0 : nullptr))
-            return rc;
-    }
-    return eval_acc_read(c, false, out_sum);
+    if (int rc = fp32_only(c, "vaeb_marginal_ll")) return rc;
+    return iw_pass(c, EvalSrc{x, n, false}, K, out_sum, out_rows);
 }
 
 int vaeb_marginal_ll_resident(vaeb_ctx* c, int32_t K, double* out_sum) {
     if (!c || !out_sum) return fail(VAEB_ERR_ARG, "null argument");
-    if (is_bf16(c)) return fail(VAEB_ERR_ARG, "vaeb_marginal_ll_resident is served by fp32 contexts");
+    if (int rc = fp32_only(c, "vaeb_marginal_ll_resident")) return rc;
     if (c->nval <= 0) return fail(VAEB_ERR_STATE, "vaeb_set_valid_data has not been called");
-    int epar = 0;
-    if (int rc = iw_begin(c, c->nval, K, &epar)) return rc;
-    const vaeb_config& g = c->c;
-    int64_t lo = 0, rows = 0;
-    valid_share(c, &lo, &rows);
-    const int chunk = g.max_eval_rows;
-    for (int64_t r0 = lo; r0 < lo + rows; r0 += chunk) {
-        const int m = (int)std::min<int64_t>(chunk, lo + rows - r0);
-        if (int rc = iw_chunk_f32(c, epar, c->xval + r0 * g.D, m, r0, K, c->eps_in ? c->eps_in + r0 * g.Z : nullptr,
-                                  c->nval, nullptr))
-            return rc;
-    }
-    return eval_acc_read(c, true, out_sum);
+    return iw_pass(c, EvalSrc{nullptr, c->nval, true}, K, out_sum, nullptr);
 }
 
 int vaeb_comm_unique_id(uint8_t out_id[128]) {
@@ -1377,8 +1366,7 @@ int vaeb_comm_init(vaeb_ctx* c, const uint8_t id_bytes[128], int32_t rank, int32
     if (r != ncclSuccess) return fail(VAEB_ERR_COMM, "ncclCommInitRank: %s", ncclGetErrorString(r));
     c->rank = rank;
     c->world = world;
-    free_graphs(c);
-    c->graph_failed = false;
+    reset_graphs(c);
     return 0;
 }
 
@@ -1450,22 +1438,22 @@ int vaeb_debug_timeline(vaeb_ctx* c, int32_t batch_index, uint64_t* out, int64_t
     if (int rc = w2_flush(c)) return rc;
     if (int rc = check_batches(c, &batch_index, 1)) return rc;
     const size_t n = (size_t)kMaxProfKernels * kDbgWG * 8;
-    if (!c->dbg)
-        if (int rc = dalloc(&c->dbg, n)) return rc;
-    HIP_TRY(hipMemsetAsync(c->dbg, 0, n * sizeof(uint64_t), c->s));
+    DevScratch tmp;   // the stamp buffer: this call's own, freed on every return
+    uint64_t* d = nullptr;
+    if (int rc = tmp.alloc(&d, (int64_t)n)) return rc;
+    HIP_TRY(hipMemsetAsync(d, 0, n * sizeof(uint64_t), c->s));
     if (int rc = upload_order(c, &batch_index, 1)) return rc;
-    c->dbg_slot = 0;
-    int rc = enqueue_train_step(c, c->par, false);
+    c->dbg = d;        // the context points at it for this one step only:
+    c->dbg_slot = 0;   // later steps (and captured graphs) run without stamps
+    const int rc = enqueue_train_step(c, c->par, false);
     if (flips(c)) c->par ^= 1;
     const int launches = c->dbg_slot;
     c->dbg_slot = 0;
-    uint64_t* d = c->dbg;
-    c->dbg = nullptr;  // later steps (and captured graphs) run without stamps
-    if (rc) { hipFree(d); return rc; }
+    c->dbg = nullptr;
+    if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->s));
     const size_t m = std::min<size_t>(n, (size_t)cap);
     HIP_TRY(hipMemcpy(out, d, m * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    hipFree(d);
     if (out_launches) *out_launches = launches;
     return 0;
 }
@@ -1673,14 +1661,14 @@ int vaeb_get_shadow(vaeb_ctx* c, uint16_t* out, int64_t n) {
     const int64_t nw = c->bf.smap.nweights;
     if (n != nw) return fail(VAEB_ERR_ARG, "size mismatch: got %lld, expected %lld", (long long)n, (long long)nw);
     if (int rc = w2_flush(c)) return rc;
+    DevScratch scratch;   // freed on every return
     bf16_t* tmp = nullptr;
-    if (int rc = dalloc(&tmp, (size_t)nw)) return rc;
+    if (int rc = scratch.alloc(&tmp, nw)) return rc;
     hipLaunchKernelGGL(bf::shadow_gather_kernel, dim3(1024), dim3(256), 0, c->s, (const bf16_t*)c->bf.shadow2[c->par], tmp,
                        c->bf.smap);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(c->s);
     if (e == hipSuccess) e = hipMemcpy(out, tmp, sizeof(bf16_t) * (size_t)nw, hipMemcpyDeviceToHost);
-    hipFree(tmp);
     if (e != hipSuccess) return fail(VAEB_ERR_HIP, "vaeb_get_shadow: %s", hipGetErrorString(e));
     return 0;
 }
