@@ -288,7 +288,8 @@ typedef struct vaeb_ae_config {
     int32_t device;
     int32_t latent;                       /* enum vaeb_ae_latent (0: the point latent)       */
     int32_t iw_samples;                   /* K of the training objective (below); 0, 1: ELBO */
-    int32_t reserved[2];
+    int32_t corruption;                   /* enum vaeb_ae_corruption (0: none), offset 112   */
+    int32_t reserved[1];
 } vaeb_ae_config;
 
 typedef struct vaeb_ae vaeb_ae;
@@ -340,7 +341,8 @@ int vaeb_ae_sq_error(vaeb_ae* ae, const float* x, int64_t n, double* out_sum, fl
  * list of the call, sample k of list position i at row k * n + i (VAEB_ERR_STATE otherwise). */
 int vaeb_ae_set_eps_mode(vaeb_ae* ae, int32_t mode, uint64_t seed);
 int vaeb_ae_push_eps(vaeb_ae* ae, const float* eps, int64_t rows);
-int vaeb_ae_set_step(vaeb_ae* ae, int64_t step);    /* Philox step counter */
+int vaeb_ae_set_step(vaeb_ae* ae, int64_t step);    /* Philox step counter; these two also on any */
+                                                    /* corrupting context (denoising training, below) */
 int vaeb_ae_get_step(vaeb_ae* ae, int64_t* step);
 /* Encoder outputs for host x [n x Dobs]: mu, log-variance and one evaluation-noise sample
  * z = mu + exp(lv / 2) eps, each [n x Dz]; any of the three may be NULL (no noise is drawn
@@ -366,6 +368,61 @@ int vaeb_ae_elbo(vaeb_ae* ae, const float* x, int64_t n, double* out_sum);
  * step or pushed eps.  Device memory does not grow with K or n (scratch sized by max_batch,
  * allocated on the first call). */
 int vaeb_ae_marginal_ll(vaeb_ae* ae, const float* x, int64_t n, int32_t K, double* out_sum, float* out_rows);
+
+/* Denoising training (extension): vaeb_ae_config.corruption != VAEB_AE_CORRUPT_NONE.  A training
+ * step on the rows idx (M rows, X = Xtr[idx]) first forms xt [M x Dobs] from X and the context's
+ * noise level p:
+ *   MASK         xt = 0 if r < p, else x
+ *   SALT_PEPPER  xt = 0 if r < p / 2;  1 if p / 2 <= r < p;  else x
+ *   GAUSS        xt = x + p n
+ * r a uniform in [0, 1) on the 2^-24 grid, n a standard normal, one draw per element (m, d).  The
+ * comparisons are float32 comparisons of exactly representable values (p / 2 is exact).  The
+ * encoder's first layer reads xt, in the forward and in its weight and bias gradient; everything
+ * that scores or reports against the data keeps the clean X: the output layer's observations (every
+ * otype, and each sample plane with iw_samples >= 2) and the returned value, which is
+ * loglik(X | enc(xt)) / M, (loglik - KL) / M, L_K / M or se / M.  The value and its gradient are
+ * those of the context's objective with the encoder's input replaced by xt; no other term
+ * appears.  This is the denoising autoencoder (POINT, ACT) and the denoising VAE (GAUSS latent);
+ * a schedule of falling levels is vaeb_ae_set_corruption_level between calls.  Valid with every
+ * latent, every otype and iw_samples >= 2 (one corruption per dataset row, shared by its K
+ * samples: the encoder runs once per row).  The evaluation calls (vaeb_ae_reconstruct, _encode,
+ * _decode, _encode_dist, _elbo, _marginal_ll, _sq_error) never corrupt: to denoise a row, pass
+ * the corrupted row to vaeb_ae_reconstruct.  Any other value of `corruption` is VAEB_ERR_ARG at
+ * create, before the device is touched.
+ *
+ * Noise, with the conventions of "Noise" above and a mode and seed of its own (default PHILOX,
+ * seed 0); vaeb_ae_set_eps_mode stays a Gaussian-latent call.  PHILOX: one Philox4x32-10 block per
+ * element under the key (seed lo, seed hi) at the counter
+ *   c0      idx[m], the dataset row: a row's corruption depends neither on the batch nor on the
+ *           position it falls in, and a row repeated in one idx list is corrupted identically
+ *   c1      0x80000000 | d.  Bit 31 marks input corruption (the latent draws have c1 < 2^30, the
+ *           FVS weight noise sets bit 30), so Dobs < 2^30 and the layout is disjoint from every
+ *           other draw
+ *   c2, c3  the training domain at the context's step counter (step, stream 0)
+ *   r = (out2 >> 8) / 2^24;  n = sqrt(-2 ln u1) cos(2 pi u2) on out0 and out1, as eps above.
+ * HOST: the caller pushes a float matrix [rows x Dobs] (r values for MASK and SALT_PEPPER, n values
+ * for GAUSS) in the order of the next training call's whole idx list, one row per list position,
+ * also with iw_samples >= 2; a training call of another row count is VAEB_ERR_STATE before the
+ * device is touched.  The push stays until the next push.
+ * The step counter: on a corrupting context every training step advances it by one, whatever the
+ * latent (a Gaussian-latent context still once per step: its latent and corruption draws of one
+ * step share the step word), and vaeb_ae_set_step / vaeb_ae_get_step are accepted.
+ * Limits: Dobs < 2^30 and max_batch * Dobs < 2^29 (VAEB_ERR_ARG at create).
+ * The five calls below are VAEB_ERR_ARG on a context created with VAEB_AE_CORRUPT_NONE. */
+enum vaeb_ae_corruption { VAEB_AE_CORRUPT_NONE = 0, VAEB_AE_CORRUPT_MASK = 1, VAEB_AE_CORRUPT_SALT_PEPPER = 2,
+                          VAEB_AE_CORRUPT_GAUSS = 3 };
+/* The level p: 0 after create.  MASK and SALT_PEPPER: 0 <= level <= 1; GAUSS: level >= 0 and
+ * finite; NaN or out of range is VAEB_ERR_ARG with the level unchanged.  The level is passed to
+ * the launches by value: no synchronise, and steps already enqueued keep theirs. */
+int vaeb_ae_set_corruption_level(vaeb_ae* ae, float level);
+int vaeb_ae_get_corruption_level(vaeb_ae* ae, float* out_level);
+/* mode: VAEB_EPS_PHILOX or VAEB_EPS_HOST. */
+int vaeb_ae_set_corruption_noise(vaeb_ae* ae, int32_t mode, uint64_t seed);
+int vaeb_ae_push_corruption(vaeb_ae* ae, const float* r, int64_t rows);
+/* The xt [n x Dobs] a training call on idx would read at the current step, level and mode (HOST:
+ * the pushed rows, which must number n).  Changes no parameter, accumulator, step or push; runs in
+ * max_batch chunks, so n need not fit max_batch. */
+int vaeb_ae_corrupt(vaeb_ae* ae, const int32_t* idx, int32_t n, float* out);
 
 #ifdef __cplusplus
 }

@@ -39,6 +39,8 @@ EXPORTS = [
     "vaeb_ae_train_many", "vaeb_ae_reconstruct", "vaeb_ae_encode", "vaeb_ae_decode",
     "vaeb_ae_set_eps_mode", "vaeb_ae_push_eps", "vaeb_ae_set_step", "vaeb_ae_get_step", "vaeb_ae_encode_dist",
     "vaeb_ae_elbo", "vaeb_ae_marginal_ll", "vaeb_ae_sq_error",
+    "vaeb_ae_set_corruption_level", "vaeb_ae_get_corruption_level", "vaeb_ae_set_corruption_noise",
+    "vaeb_ae_push_corruption", "vaeb_ae_corrupt",
 ]
 DIAG_EXPORTS = ["vaeb_profile_steps", "vaeb_kernel_name", "vaeb_debug_timeline", "vaeb_test_gemm_bf16",
                 "vaeb_bench_gemm_bf16", "vaeb_graph_status", "vaeb_comm_info", "vaeb_time_update_many", "vaeb_busy",
@@ -48,6 +50,7 @@ AE_MAX_LAYERS = 8
 AE_BINARY, AE_CONT, AE_SE = 0, 1, 2
 AE_OTYPE = {"binary": AE_BINARY, "cont": AE_CONT, "se": AE_SE}
 AE_LATENT = {"point": 0, "gauss": 1, "act": 3}   # 2 is unassigned
+AE_CORRUPTION = {"none": 0, "mask": 1, "saltpepper": 2, "gauss": 3}   # enum vaeb_ae_corruption
 ACT = {"tanh": 0, "sigmoid": 1, "relu": 2}
 
 
@@ -68,7 +71,7 @@ class AEConfigC(ctypes.Structure):
         ("Dz", ctypes.c_int32), ("n_dec", ctypes.c_int32), ("Ddec", ctypes.c_int32 * 8),
         ("otype", ctypes.c_int32), ("act", ctypes.c_int32), ("s2", ctypes.c_float), ("eta", ctypes.c_float),
         ("max_batch", ctypes.c_int32), ("device", ctypes.c_int32), ("latent", ctypes.c_int32),
-        ("iw_samples", ctypes.c_int32), ("reserved", ctypes.c_int32 * 2),
+        ("iw_samples", ctypes.c_int32), ("corruption", ctypes.c_int32), ("reserved", ctypes.c_int32 * 1),
     ]
 
 
@@ -177,6 +180,11 @@ def load():
         "vaeb_ae_elbo": ([_P, _F, _I64, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
         "vaeb_ae_marginal_ll": ([_P, _F, _I64, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), _F], ctypes.c_int),
         "vaeb_ae_sq_error": ([_P, _F, _I64, ctypes.POINTER(ctypes.c_double), _F], ctypes.c_int),
+        "vaeb_ae_set_corruption_level": ([_P, ctypes.c_float], ctypes.c_int),
+        "vaeb_ae_get_corruption_level": ([_P, _F], ctypes.c_int),
+        "vaeb_ae_set_corruption_noise": ([_P, ctypes.c_int32, ctypes.c_uint64], ctypes.c_int),
+        "vaeb_ae_push_corruption": ([_P, _F, _I64], ctypes.c_int),
+        "vaeb_ae_corrupt": ([_P, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, _F], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -549,10 +557,13 @@ class AEContext:
     """One degenerate-vae autoencoder (vaeb_ae_*) on one GPU; latent="gauss": the deep VAE on
     the same layer stack (include/vaeb_hip.h enum vaeb_ae_latent); iw_samples = K >= 2: train on
     the K-sample importance-weighted bound (K * len(idx) <= max_batch per step).  otype="se" with
-    latent="act" is the vanilla squared-error autoencoder (vanilla-ae/ae.py): train returns se / n."""
+    latent="act" is the vanilla squared-error autoencoder (vanilla-ae/ae.py): train returns se / n.
+    corruption="mask" | "saltpepper" | "gauss": denoising training (enum vaeb_ae_corruption): the
+    encoder's first layer reads the rows corrupted at set_corruption_level's level, the output is
+    scored on the clean rows; the evaluation calls never corrupt."""
 
     def __init__(self, Dobs, Denc, Dz, Ddec, otype="binary", act="tanh", s2=1.0, eta=0.01, max_batch=100,
-                 device=0, latent="point", iw_samples=1):
+                 device=0, latent="point", iw_samples=1, corruption="none"):
         self.lib = load()
         c = AEConfigC()
         c.Dobs, c.Dz = int(Dobs), int(Dz)
@@ -575,6 +586,10 @@ class AEContext:
         c.latent = AE_LATENT[latent]
         c.iw_samples = int(iw_samples)
         self.iw_samples = c.iw_samples
+        if corruption not in AE_CORRUPTION:
+            raise VaebError(f"corruption {corruption!r} not supported (none | mask | saltpepper | gauss)")
+        c.corruption = AE_CORRUPTION[corruption]
+        self.corruption = corruption
         self.cfg = c
         self.Dobs, self.Dz = c.Dobs, c.Dz
         self.h = _P()
@@ -696,3 +711,29 @@ class AEContext:
         """K-sample importance-weighted estimate of sum_i log p(x_i) (vaeb_ae_marginal_ll); with
         rows=True also the per-row values: (sum, [n])."""
         return self._sum_rows(self.lib.vaeb_ae_marginal_ll, x, rows, int(K))
+
+    # ---- denoising training (corruption != "none") ----
+    def set_corruption_level(self, level):
+        check(self.lib.vaeb_ae_set_corruption_level(self.h, float(level)))
+
+    def get_corruption_level(self):
+        out = ctypes.c_float()
+        check(self.lib.vaeb_ae_get_corruption_level(self.h, ctypes.byref(out)))
+        return out.value
+
+    def set_corruption_noise(self, mode, seed=0):
+        check(self.lib.vaeb_ae_set_corruption_noise(self.h, int(mode), int(seed)))
+
+    def push_corruption(self, r):
+        """Host corruption noise: r [rows x Dobs] (uniforms for mask / saltpepper, normals for gauss)
+        in the order of the next training call's whole idx list."""
+        r = np.ascontiguousarray(r, np.float32).reshape(-1, self.Dobs)
+        check(self.lib.vaeb_ae_push_corruption(self.h, fptr(r), r.shape[0]))
+
+    def corrupt(self, idx):
+        """The corrupted rows [len(idx) x Dobs] a training call on idx would read at the current step,
+        level and noise mode (vaeb_ae_corrupt); changes no state."""
+        idx = np.ascontiguousarray(idx, np.int32)
+        out = np.empty((idx.size, self.Dobs), np.float32)
+        check(self.lib.vaeb_ae_corrupt(self.h, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), idx.size, fptr(out)))
+        return out

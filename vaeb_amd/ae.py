@@ -16,6 +16,14 @@ heads, z = mu + exp(lv / 2) eps with device Philox noise, and train(idx) returni
 `ConstructVanillaAE` mirrors the reference's vanilla-ae/ae.py:45-112, the squared-error baseline of
 its report: the code goes through f, Z = f(Hz Wz + bz), there is no prior on Z, the output is
 Xpr = sigmoid(.), logjoint = -se + weight decay, and train(idx) returns se / len(idx).
+
+Denoising training (extension; the reference report's "Scheduled VAEB" follow-up): each constructor
+takes `corruption=` "mask" | "saltpepper" | "gauss" or (kind, level) and an optional
+`corruption_seed`.  The encoder then reads the rows corrupted at the current noise level while the
+output is scored on the clean rows (include/vaeb_hip.h enum vaeb_ae_corruption): the denoising
+autoencoder, and with ConstructVAE the denoising VAE.  train.set_noise(level), train.noise and
+train.corrupt(idx) steer and show the corruption; noise_schedule and train_epochs(noise=...) run a
+schedule of falling levels.
 """
 from __future__ import annotations
 
@@ -97,9 +105,45 @@ class _AccArena:
         self.ctx.set_adagrad_state(flat)
 
 
-def _construct(latent, Xtr, Denc, Dz, Ddec, f, s2, inf, otype, max_batch, device, iw_samples=1):
+CORRUPTIONS = ("mask", "saltpepper", "gauss")
+
+
+def _corruption(corruption):
+    """(kind, level) of a constructor's corruption argument: None, a kind, or (kind, level)."""
+    if corruption is None:
+        return "none", 0.0
+    kind, level = (corruption, 0.0) if isinstance(corruption, str) else corruption
+    if kind not in CORRUPTIONS:
+        raise ValueError(f"corruption {kind!r} not supported (mask | saltpepper | gauss)")
+    return kind, float(level)
+
+
+class _DenoisingTrain:
+    """train(idx) of a corrupting context: callable as the plain train function, with the noise
+    level of the steps to come (set_noise / noise) and the corrupted rows a step would read."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+
+    def __call__(self, idx):
+        return self.ctx.train(np.asarray(idx, np.int32))
+
+    def set_noise(self, level):
+        self.ctx.set_corruption_level(level)
+
+    @property
+    def noise(self):
+        return self.ctx.get_corruption_level()
+
+    def corrupt(self, idx):
+        return self.ctx.corrupt(np.asarray(idx, np.int32))
+
+
+def _construct(latent, Xtr, Denc, Dz, Ddec, f, s2, inf, otype, max_batch, device, iw_samples=1, corruption=None,
+               corruption_seed=0):
     """The shared body of ConstructAE / ConstructVAE / ConstructVanillaAE; returns (train, ctx, theta),
     train(idx) being one step of the engine on the rows Xtr[idx] with train.ctx = ctx."""
+    kind, level = _corruption(corruption)
     if otype not in ("binary", "cont") and (latent, otype) != ("act", "se"):
         raise ValueError("otype currently only supports binary.")   # ae.py:74-75 (and cont)
     inf = inf if inf is not None else AdaGrad(0.01)
@@ -112,7 +156,7 @@ def _construct(latent, Xtr, Denc, Dz, Ddec, f, s2, inf, otype, max_batch, device
     K = max(1, int(iw_samples))   # the K sample planes of a step are stacked inside max_batch
     mb = int(max_batch) if max_batch else max(100 * K, min(4096, Xtr.shape[0]))
     ctx = _lib.AEContext(Dobs, Denc, Dz, Ddec, otype=otype, act=_act_name(f), s2=s2, eta=inf.eta, max_batch=mb,
-                         device=device, latent=latent, iw_samples=iw_samples)
+                         device=device, latent=latent, iw_samples=iw_samples, corruption=kind)
     ctx.set_data(Xtr)
     ctx.set_params(np.concatenate([t.ravel() for t in theta0]))
     offs = np.cumsum([0] + [int(np.prod(s)) for _, s in shapes])
@@ -122,6 +166,11 @@ def _construct(latent, Xtr, Denc, Dz, Ddec, f, s2, inf, otype, max_batch, device
     updates = inf.construct(arena, theta)
     bind_updates(arena, theta, updates)
 
+    if kind != "none":
+        ctx.set_corruption_noise(_lib.EPS_PHILOX, corruption_seed)
+        ctx.set_corruption_level(level)
+        return _DenoisingTrain(ctx), ctx, theta
+
     def train(idx):
         return ctx.train(np.asarray(idx, np.int32))
 
@@ -130,14 +179,16 @@ def _construct(latent, Xtr, Denc, Dz, Ddec, f, s2, inf, otype, max_batch, device
 
 
 def ConstructAE(Xtr, Denc=(500,), Dz=20, Ddec=(500,), f="tanh", s2=1.0, inf=None, otype="binary",
-                max_batch=None, device=0):
-    """ae.py:41-117.  Returns (train, reconstruct, encode, decode, theta)."""
-    train, ctx, theta = _construct("point", Xtr, Denc, Dz, Ddec, f, s2, inf, otype, max_batch, device)
+                max_batch=None, device=0, corruption=None, corruption_seed=0):
+    """ae.py:41-117.  Returns (train, reconstruct, encode, decode, theta).  corruption: the denoising
+    autoencoder (module docstring); None: the reference's model, theta_0 and steps."""
+    train, ctx, theta = _construct("point", Xtr, Denc, Dz, Ddec, f, s2, inf, otype, max_batch, device,
+                                   corruption=corruption, corruption_seed=corruption_seed)
     return train, ctx.reconstruct, ctx.encode, ctx.decode, theta
 
 
 def ConstructVAE(Xtr, Denc=(500,), Dz=20, Ddec=(500,), f="tanh", s2=1.0, inf=None, otype="binary", seed=10,
-                 max_batch=None, device=0, iw_samples=1):
+                 max_batch=None, device=0, iw_samples=1, corruption=None, corruption_seed=0):
     """ConstructAE with a Gaussian latent: the same five return values, theta in the order
     [..., Wzmu, Wzlv, bzmu, bzlv, ...].  train(idx) takes one AdaGrad step on the ELBO of the
     rows Xtr[idx] (one Philox draw per row and latent, keyed by `seed`, the dataset row and the
@@ -148,8 +199,11 @@ def ConstructVAE(Xtr, Denc=(500,), Dz=20, Ddec=(500,), f="tanh", s2=1.0, inf=Non
     values) -- the figure that ranks a deep model against the one-hidden-layer VAEB's
     marginal_likelihood).  iw_samples = K >= 2: train(idx) steps on the K-sample importance-weighted
     bound instead (K draws per row, sample stream k) and returns that bound / len(idx); a step needs
-    K * len(idx) <= max_batch, which defaults to max(100 K, min(4096, N)).  train.iw_samples is K."""
-    train, ctx, theta = _construct("gauss", Xtr, Denc, Dz, Ddec, f, s2, inf, otype, max_batch, device, iw_samples)
+    K * len(idx) <= max_batch, which defaults to max(100 K, min(4096, N)).  train.iw_samples is K.
+    corruption: the denoising VAE (the encoder sees the corrupted rows, the bound is scored on the clean
+    ones; `corruption_seed` keys the corruption, `seed` the latent noise)."""
+    train, ctx, theta = _construct("gauss", Xtr, Denc, Dz, Ddec, f, s2, inf, otype, max_batch, device, iw_samples,
+                                   corruption=corruption, corruption_seed=corruption_seed)
     ctx.set_eps_mode(_lib.EPS_PHILOX, seed)
     train.iw_samples = ctx.iw_samples
     train.elbo = lambda X: ctx.elbo(_values(X))
@@ -157,13 +211,16 @@ def ConstructVAE(Xtr, Denc=(500,), Dz=20, Ddec=(500,), f="tanh", s2=1.0, inf=Non
     return train, ctx.reconstruct, ctx.encode, ctx.decode, theta
 
 
-def ConstructVanillaAE(Xtr, Denc=(500,), Dz=20, Ddec=(500,), f="tanh", s2=1.0, inf=None, max_batch=None, device=0):
+def ConstructVanillaAE(Xtr, Denc=(500,), Dz=20, Ddec=(500,), f="tanh", s2=1.0, inf=None, max_batch=None, device=0,
+                       corruption=None, corruption_seed=0):
     """vanilla-ae/ae.py:45-112.  Returns (train, reconstruct, encode, decode, theta): train(idx) takes
     one AdaGrad step up -se + weight decay on the rows Xtr[idx] and returns se / len(idx) (positive);
     encode(X) is the activated code f(Hz Wz + bz).  theta_0 is drawn from the global numpy RNG in the
     order of ConstructAE with a binary output.  train.ctx is the engine context; train.mse(X) is
-    mse(X, reconstruct(X)) computed on the device (vaeb_ae_sq_error), nothing but the sum coming back."""
-    train, ctx, theta = _construct("act", Xtr, Denc, Dz, Ddec, f, s2, inf, "se", max_batch, device)
+    mse(X, reconstruct(X)) computed on the device (vaeb_ae_sq_error), nothing but the sum coming back.
+    corruption: the denoising autoencoder; train.mse(X) stays the clean reconstruction error."""
+    train, ctx, theta = _construct("act", Xtr, Denc, Dz, Ddec, f, s2, inf, "se", max_batch, device,
+                                   corruption=corruption, corruption_seed=corruption_seed)
 
     def device_mse(X):
         X = _values(X)
@@ -183,12 +240,26 @@ def rmse(X, Xpr):
     return float(np.sqrt(np.mean(np.sum((X - Xpr) ** 2, 1))))
 
 
-def train_epochs(train, Ntr, epochs, batch_size=100, verbose=True):
+def noise_schedule(levels, epochs):
+    """The per-epoch noise levels of a schedule of len(levels) stages over `epochs` epochs: epoch e
+    uses levels[min(len(levels) - 1, e * len(levels) // epochs)]."""
+    levels = list(levels)
+    if not levels:
+        raise ValueError("noise_schedule needs at least one level")
+    return [levels[min(len(levels) - 1, e * len(levels) // epochs)] for e in range(epochs)]
+
+
+def train_epochs(train, Ntr, epochs, batch_size=100, verbose=True, noise=None):
     """The LearnMNIST / LearnFreyFace loop (ae.py:140-151, 179-190): a fresh global-RNG
     permutation per epoch, batches of batch_size with the last partial batch kept.  The
-    whole epoch is enqueued with one host sync (vaeb_ae_train_many)."""
+    whole epoch is enqueued with one host sync (vaeb_ae_train_many).  noise: one level per epoch
+    (noise_schedule), set before the epoch's steps on a train built with a corruption."""
+    if noise is not None and len(noise) != epochs:
+        raise ValueError(f"noise holds {len(noise)} levels for {epochs} epochs")
     loglik = []
     for i in range(epochs):
+        if noise is not None:
+            train.set_noise(noise[i])
         idx = np.random.permutation(np.arange(Ntr)).astype(np.int32)
         loglik.extend(train.ctx.train_many(idx, batch_size).tolist())
         if verbose:

@@ -2,7 +2,10 @@
 // deep VAEs on the fp32 tile engine's kernels (ae_mlp.hpp, ae_iwae.hpp).  Included by
 // vaeb_hip.hip after the VAEB helpers.  Each call and the helper sequence it runs:
 //   vaeb_ae_train(_many)  per batch ae_step: ae_encode | ae_decode_hidden | ae_output(TRAIN) | the value
-//                         (iw_samples >= 2: ae_iw_forward instead), then ae_bwd_decoder | ae_bwd_encoder
+//                         (iw_samples >= 2: ae_iw_forward instead), then ae_bwd_decoder | ae_bwd_encoder;
+//                         on a corrupting context ae_corrupt_rows first: ae_encode and ae_bwd_encoder read
+//                         its xt, everything else the clean rows
+//   vaeb_ae_corrupt       chunks of max_batch: ae_corrupt_rows, xt to the host
 //   vaeb_ae_reconstruct   ae_chunks: ae_encode (zero noise) | ae_decode_hidden | ae_output(PREDICT)
 //   vaeb_ae_encode        ae_chunks: ae_encode (zero noise)
 //   vaeb_ae_decode        ae_chunks: ae_decode_hidden on the caller's z | ae_output(PREDICT)
@@ -58,6 +61,15 @@ struct vaeb_ae {
     int64_t step = 0;                 // Philox step counter
     float* eps_in = nullptr;          // pushed host eps [eps_rows x Dz]
     int64_t eps_rows = 0, eps_cap = 0;
+    // input corruption (c.corruption != VAEB_AE_CORRUPT_NONE; ae_corrupt.hpp): the corrupted rows
+    // xt [max_batch x Dobs] (allocated at create), the level, and a noise mode, seed and pushed
+    // draws [cor_rows x Dobs] of its own; the step counter is the one above
+    float* xc = nullptr;
+    float cor_level = 0.f;
+    int cor_mode = VAEB_EPS_PHILOX;
+    uint64_t cor_seed = 0;
+    float* cor_in = nullptr;
+    int64_t cor_rows = 0, cor_cap = 0;
 };
 
 namespace {
@@ -65,6 +77,7 @@ namespace {
 bool ae_gauss(const vaeb_ae* a) { return a->c.latent == VAEB_AE_LATENT_GAUSS; }
 bool ae_act_latent(const vaeb_ae* a) { return a->c.latent == VAEB_AE_LATENT_ACT; }
 bool ae_iw(const vaeb_ae* a) { return a->c.iw_samples >= 2; }
+bool ae_corrupting(const vaeb_ae* a) { return a->c.corruption != VAEB_AE_CORRUPT_NONE; }
 
 // vaeb_ae_marginal_ll's and the importance-weighted step's scratch, sized by max_batch
 int ae_iw_scratch(vaeb_ae* a) {
@@ -94,6 +107,26 @@ int ae_host_eps_ready(const vaeb_ae* a, int64_t rows) {
     if (a->eps_mode == VAEB_EPS_HOST && a->eps_rows != rows)
         return fail(VAEB_ERR_STATE, "host eps mode: pushed %lld rows, the call needs %lld (call vaeb_ae_push_eps)",
                     (long long)a->eps_rows, (long long)rows);
+    return 0;
+}
+
+int ae_host_corruption_ready(const vaeb_ae* a, int64_t rows) {
+    if (ae_corrupting(a) && a->cor_mode == VAEB_EPS_HOST && a->cor_rows != rows)
+        return fail(VAEB_ERR_STATE, "host corruption noise: pushed %lld rows, the call needs %lld (call vaeb_ae_push_corruption)",
+                    (long long)a->cor_rows, (long long)rows);
+    return 0;
+}
+
+// xt = the M dataset rows idx, corrupted at the context's level and step, into a->xc.  lb: the
+// rows' offset in the call's idx list (host mode: the pushed draws of list position lb + m).
+int ae_corrupt_rows(vaeb_ae* a, const int* idx, int M, int64_t lb) {
+    ae::AeCorruptArgs q{};
+    q.X = a->data; q.x_rows = (int)a->nrows; q.idx = idx; q.M = M; q.D = a->c.Dobs;
+    q.kind = a->c.corruption; q.level = a->cor_level;
+    q.rin = a->cor_mode == VAEB_EPS_HOST ? a->cor_in + lb * a->c.Dobs : nullptr;
+    q.seed = a->cor_seed; q.step = a->step; q.out = a->xc;
+    hipLaunchKernelGGL(ae::ae_corrupt_kernel, dim3(cdiv(M * a->c.Dobs, 256)), dim3(256), 0, a->s, q);
+    CHECK_LAUNCH();
     return 0;
 }
 
@@ -254,11 +287,12 @@ int ae_bwd_encoder(vaeb_ae* a, const AeRows& x, int M) {
 // ae_iwae.hpp): the encoder once on the M rows, the decoder on the K * M stacked rows
 // (g = k * M + m) with the output deltas scaled by the normalised weights.  L_K / M -> outs[slot].
 // lb: the step's offset in the call's idx list of n rows (host eps: sample k of list position i
-// at row k * n + i).
-int ae_iw_forward(vaeb_ae* a, const AeRows& x, int M, int slot, int64_t lb, int64_t n) {
+// at row k * n + i).  xe: the encoder's input rows (x, or its corrupted copy); x keeps the row
+// identity (the Philox c0) and the observations.
+int ae_iw_forward(vaeb_ae* a, const AeRows& xe, const AeRows& x, int M, int slot, int64_t lb, int64_t n) {
     const vaeb_ae_config& g = a->c;
     const int D = g.Dobs, K = g.iw_samples, KM = K * M;
-    if (int rc = ae_encode(a, x, M, AeNoise{})) return rc;   // mu, lv
+    if (int rc = ae_encode(a, xe, M, AeNoise{})) return rc;   // mu, lv
     ae::AeIwArgs q{};
     q.Dz = g.Dz; q.R = M; q.S = K; q.k0 = 0; q.row0 = lb; q.n = n;
     q.eps_mode = a->eps_mode == VAEB_EPS_HOST ? 1 : 0;
@@ -282,6 +316,10 @@ int ae_iw_forward(vaeb_ae* a, const AeRows& x, int M, int slot, int64_t lb, int6
 // train(idx) on the M dataset rows idx (the slice at offset lb of the call's list of n rows):
 // forward + value, then the backward.  loglik / M -> outs[slot]; Gaussian latent: (loglik - KL) / M,
 // eps drawn at the step counter, which then advances (the one place; point contexts have none).
+// A corrupting context: the encoder's input rows xe are the corrupted copy a->xc of x (drawn at
+// the same step counter, which advances once whatever the latent), read by the first layer's
+// forward and weight gradient; the observations, the latent draw's c0 and the host-eps offsets
+// stay those of x and idx.  Without corruption xe is x: the launches are what they were.
 // Squared-error output: the partials are se, so outs[slot] = se / M (positive) while the deltas
 // are those of -se.  iw_samples >= 2: ae_iw_forward, the decoder's backward on the K * M stacked
 // rows, the K planes of dmu / dlv summed, then the encoder's backward on M rows as ever.
@@ -289,11 +327,16 @@ int ae_step(vaeb_ae* a, const int* idx, int M, int slot, int64_t lb, int64_t n) 
     const vaeb_ae_config& g = a->c;
     const bool gauss = ae_gauss(a), iw = ae_iw(a);
     const AeRows x{a->data, (int)a->nrows, idx};
+    AeRows xe = x;
+    if (ae_corrupting(a)) {
+        if (int rc = ae_corrupt_rows(a, idx, M, lb)) return rc;
+        xe = AeRows{a->xc, M, nullptr};
+    }
     const int R = iw ? g.iw_samples * M : M;
     if (iw) {
-        if (int rc = ae_iw_forward(a, x, M, slot, lb, n)) return rc;
+        if (int rc = ae_iw_forward(a, xe, x, M, slot, lb, n)) return rc;
     } else {
-        if (int rc = ae_encode(a, x, M, AeNoise{AE_EPS_TRAIN, idx, lb})) return rc;
+        if (int rc = ae_encode(a, xe, M, AeNoise{AE_EPS_TRAIN, idx, lb})) return rc;
         if (int rc = ae_decode_hidden(a, a->Z, M)) return rc;
         if (int rc = ae_output(a, M, AE_OUT_TRAIN, x)) return rc;
         if (gauss)
@@ -311,8 +354,8 @@ int ae_step(vaeb_ae* a, const int* idx, int M, int slot, int64_t lb, int64_t n) 
                            M, g.Dz, g.iw_samples);
         CHECK_LAUNCH();
     }
-    if (int rc = ae_bwd_encoder(a, x, M)) return rc;
-    if (gauss) ++a->step;
+    if (int rc = ae_bwd_encoder(a, xe, M)) return rc;
+    if (gauss || ae_corrupting(a)) ++a->step;
     return 0;
 }
 
@@ -411,6 +454,13 @@ int vaeb_ae_create(const vaeb_ae_config* cfg, vaeb_ae** out) {
         return fail(VAEB_ERR_ARG, "iw_samples = %d: 0 to 2^20 (the Philox sample-stream field)", g.iw_samples);
     if (g.iw_samples >= 2 && g.latent != VAEB_AE_LATENT_GAUSS)
         return fail(VAEB_ERR_ARG, "iw_samples = %d needs a VAEB_AE_LATENT_GAUSS context", g.iw_samples);
+    if (g.corruption < VAEB_AE_CORRUPT_NONE || g.corruption > VAEB_AE_CORRUPT_GAUSS)
+        return fail(VAEB_ERR_ARG, "corruption must be VAEB_AE_CORRUPT_NONE | _MASK | _SALT_PEPPER | _GAUSS (got %d)",
+                    g.corruption);
+    if (g.corruption != VAEB_AE_CORRUPT_NONE && g.Dobs >= (1 << 30))
+        return fail(VAEB_ERR_ARG, "corruption needs Dobs < 2^30 (the Philox c1 field)");
+    if (g.corruption != VAEB_AE_CORRUPT_NONE && (int64_t)g.max_batch * g.Dobs >= (1 << 29))
+        return fail(VAEB_ERR_ARG, "corruption needs max_batch * Dobs < 2^29 (the corrupted rows' 32-bit byte offsets)");
     auto* a = new vaeb_ae();
     a->c = g;
     if (hipSetDevice(g.device) != hipSuccess || hipStreamCreateWithFlags(&a->s, hipStreamNonBlocking) != hipSuccess) {
@@ -464,6 +514,7 @@ int vaeb_ae_create(const vaeb_ae_config* cfg, vaeb_ae** out) {
         rc = rc ? rc : a->mem.alloc(&a->iw_val, B);
         rc = rc ? rc : a->mem.alloc(&a->iw_lw, B);
     }
+    if (ae_corrupting(a)) rc = rc ? rc : a->mem.alloc(&a->xc, B * g.Dobs);
     rc = rc ? rc : ae_reserve(a, (int)B, 1);
     a->out.d[0] = a->dA; a->out.d[1] = a->dA2;
     a->lat.d[0] = ae_gauss(a) ? a->dmu : a->dZ; a->lat.d[1] = a->dlv;
@@ -512,6 +563,7 @@ int vaeb_ae_train_many(vaeb_ae* a, const int32_t* idx, int32_t n, int32_t batch,
                     a->c.iw_samples, std::min(batch, n), a->c.max_batch);
     if (ae_gauss(a))
         if (int rc = ae_host_eps_ready(a, iw ? (int64_t)a->c.iw_samples * n : (int64_t)n)) return rc;
+    if (int rc = ae_host_corruption_ready(a, n)) return rc;
     const int nb = cdiv(n, batch);
     if (int rc = ae_reserve(a, n, nb)) return rc;
     HIP_TRY(hipMemcpyAsync(a->idx, idx, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, a->s));
@@ -561,6 +613,19 @@ int vaeb_ae_sq_error(vaeb_ae* a, const float* x, int64_t n, double* out_sum, flo
         if (!ae_gauss(a)) return fail(VAEB_ERR_ARG, fn " needs a VAEB_AE_LATENT_GAUSS context");        \
     } while (0)
 
+// the step counter: Gaussian-latent and corrupting contexts draw at it
+#define AE_NEED_STEP(a, fn)                                                                             \
+    do {                                                                                                \
+        if (!(a)) return fail(VAEB_ERR_ARG, "null argument");                                           \
+        if (!ae_gauss(a) && !ae_corrupting(a))                                                          \
+            return fail(VAEB_ERR_ARG, fn " needs a VAEB_AE_LATENT_GAUSS or a corrupting context");      \
+    } while (0)
+#define AE_NEED_CORRUPT(a, fn)                                                                          \
+    do {                                                                                                \
+        if (!(a)) return fail(VAEB_ERR_ARG, "null argument");                                           \
+        if (!ae_corrupting(a)) return fail(VAEB_ERR_ARG, fn " needs a context created with a corruption"); \
+    } while (0)
+
 int vaeb_ae_set_eps_mode(vaeb_ae* a, int32_t mode, uint64_t seed) {
     AE_NEED_GAUSS(a, "vaeb_ae_set_eps_mode");
     if (mode != VAEB_EPS_PHILOX && mode != VAEB_EPS_HOST) return fail(VAEB_ERR_ARG, "bad eps mode");
@@ -583,13 +648,13 @@ int vaeb_ae_push_eps(vaeb_ae* a, const float* eps, int64_t rows) {
 }
 
 int vaeb_ae_set_step(vaeb_ae* a, int64_t step) {
-    AE_NEED_GAUSS(a, "vaeb_ae_set_step");
+    AE_NEED_STEP(a, "vaeb_ae_set_step");
     a->step = step;
     return 0;
 }
 
 int vaeb_ae_get_step(vaeb_ae* a, int64_t* step) {
-    AE_NEED_GAUSS(a, "vaeb_ae_get_step");
+    AE_NEED_STEP(a, "vaeb_ae_get_step");
     if (!step) return fail(VAEB_ERR_ARG, "null argument");
     *step = a->step;
     return 0;
@@ -673,5 +738,62 @@ int vaeb_ae_marginal_ll(vaeb_ae* a, const float* x, int64_t n, int32_t K, double
     return 0;
 }
 #undef AE_NEED_GAUSS
+#undef AE_NEED_STEP
+
+// ------------------------------------------------------------------ input corruption
+int vaeb_ae_set_corruption_level(vaeb_ae* a, float level) {
+    AE_NEED_CORRUPT(a, "vaeb_ae_set_corruption_level");
+    const bool unit = a->c.corruption != VAEB_AE_CORRUPT_GAUSS;
+    if (!(level >= 0.f) || (unit ? level > 1.f : !std::isfinite(level)))   // NaN fails the first
+        return fail(VAEB_ERR_ARG, unit ? "corruption level %g: 0 to 1" : "corruption level %g: finite and >= 0", (double)level);
+    a->cor_level = level;   // a launch argument: the enqueued steps keep theirs
+    return 0;
+}
+
+int vaeb_ae_get_corruption_level(vaeb_ae* a, float* out) {
+    AE_NEED_CORRUPT(a, "vaeb_ae_get_corruption_level");
+    if (!out) return fail(VAEB_ERR_ARG, "null argument");
+    *out = a->cor_level;
+    return 0;
+}
+
+int vaeb_ae_set_corruption_noise(vaeb_ae* a, int32_t mode, uint64_t seed) {
+    AE_NEED_CORRUPT(a, "vaeb_ae_set_corruption_noise");
+    if (mode != VAEB_EPS_PHILOX && mode != VAEB_EPS_HOST) return fail(VAEB_ERR_ARG, "bad corruption noise mode");
+    HIP_TRY(hipStreamSynchronize(a->s));
+    a->cor_mode = mode;
+    a->cor_seed = seed;
+    return 0;
+}
+
+int vaeb_ae_push_corruption(vaeb_ae* a, const float* r, int64_t rows) {
+    AE_NEED_CORRUPT(a, "vaeb_ae_push_corruption");
+    if (!r || rows <= 0) return fail(VAEB_ERR_ARG, "bad corruption noise arguments");
+    const int64_t n = rows * a->c.Dobs;
+    HIP_TRY(hipStreamSynchronize(a->s));
+    if (n > a->cor_cap) a->cor_rows = 0;   // the old rows go with the old buffer
+    if (int rc = a->mem.grow(&a->cor_in, &a->cor_cap, n)) return rc;
+    HIP_TRY(hipMemcpy(a->cor_in, r, sizeof(float) * (size_t)n, hipMemcpyHostToDevice));
+    a->cor_rows = rows;
+    return 0;
+}
+
+int vaeb_ae_corrupt(vaeb_ae* a, const int32_t* idx, int32_t n, float* out) {
+    AE_NEED_CORRUPT(a, "vaeb_ae_corrupt");
+    if (!idx || !out || n <= 0) return fail(VAEB_ERR_ARG, "bad arguments");
+    if (int rc = ae_check_idx(a, idx, n)) return rc;
+    if (int rc = ae_host_corruption_ready(a, n)) return rc;
+    if (int rc = ae_reserve(a, n, 1)) return rc;
+    const int D = a->c.Dobs;
+    HIP_TRY(hipMemcpyAsync(a->idx, idx, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, a->s));
+    for (int64_t lb = 0; lb < n; lb += a->c.max_batch) {
+        const int m = (int)std::min<int64_t>(a->c.max_batch, n - lb);
+        if (int rc = ae_corrupt_rows(a, a->idx + lb, m, lb)) return rc;
+        HIP_TRY(hipMemcpyAsync(out + lb * D, a->xc, sizeof(float) * (size_t)m * D, hipMemcpyDeviceToHost, a->s));
+        HIP_TRY(hipStreamSynchronize(a->s));
+    }
+    return 0;
+}
+#undef AE_NEED_CORRUPT
 
 }  // extern "C"

@@ -45,6 +45,7 @@
 #include "h16_engines.hpp"
 #include "ae_mlp.hpp"
 #include "ae_iwae.hpp"
+#include "ae_corrupt.hpp"
 
 using namespace vaeb;
 
@@ -576,7 +577,7 @@ const char* vaeb_last_error(void) { return g_err.c_str(); }
 
 int vaeb_version(int32_t* major, int32_t* minor) {
     if (major) *major = 0;
-    if (minor) *minor = 2;
+    if (minor) *minor = 3;
     return 0;
 }
 

@@ -2,7 +2,7 @@
 main, the squared-error autoencoder baseline behind reconstruction_res/AE_MSE.res.
 
     python -m vaeb_amd.vanilla_ae [--synthetic] [--out DIR] [--epochs N] [--dz 2,10,20]
-                                  [--hidden H] [--ntr N]
+                                  [--hidden H] [--ntr N] [--corruption KIND [--noise L0,L1,...]]
 
 main() seeds the global numpy RNG with 15485863 (:219), then for Dz in 2, 10, 20 trains the Frey
 model (hidden 200, 1500 rows, 100 epochs at Dz = 2, otherwise 550) and the MNIST model (hidden 500,
@@ -11,6 +11,11 @@ batch kept, saves the eight AE_{continuous,discrete}_{Dz}_{orig,recon}_{t}.jpg p
 test set's MSE to AE_MSE.res.  All compute runs in libvaeb_hip.so (ae.ConstructVanillaAE); an epoch
 is one vaeb_ae_train_many call and the test MSE is reduced on the device (vaeb_ae_sq_error).  The
 commented-out matplotlib learning curves of the reference are not written.
+
+--corruption mask|saltpepper|gauss trains every model as a denoising autoencoder (the encoder reads
+the corrupted rows, the error is taken on the clean ones); --noise L0,L1,... is a schedule of stages
+spread over each model's epochs by ae.noise_schedule (default: one stage at 0.3).  AE_MSE.res stays the
+clean test-set MSE.  Without --corruption nothing changes.
 
 Data comes through cli.load_dataset (freyfaces.pkl / mnist.pkl.gz in the working directory, or the
 synthetic stand-ins with --synthetic).  MNIST follows data.py:11-21: the training rows are the first
@@ -52,17 +57,36 @@ def load_mnist(Ntr=50000, synthetic=False):
     return np.vstack((xtr, xva))[:Ntr], xte
 
 
-def _learn(Xtr, Xte, epochs, Dz, hidden, batch_size=100):
-    """The shared body of LearnFreyFace / LearnMNIST (ae.py:136-166, 181-211)."""
+DEFAULT_NOISE = [0.3]
+
+
+def corruption_args(kind, noise):
+    """The checked (kind, stage list) of --corruption / --noise, or None without --corruption."""
+    if kind is None:
+        if noise is not None:
+            raise ValueError("--noise needs --corruption mask|saltpepper|gauss")
+        return None
+    if kind not in ae.CORRUPTIONS:
+        raise ValueError(f"--corruption {kind!r} not supported (mask | saltpepper | gauss)")
+    return kind, list(noise) if noise is not None else list(DEFAULT_NOISE)
+
+
+def _learn(Xtr, Xte, epochs, Dz, hidden, batch_size=100, corruption=None):
+    """The shared body of LearnFreyFace / LearnMNIST (ae.py:136-166, 181-211).  corruption: (kind,
+    stage list) of a denoising run, the stages spread over the epochs."""
     Xtr, Xte = np.asarray(Xtr, np.float32), np.asarray(Xte, np.float32)
     Ntr = Xtr.shape[0]
     if Xte.shape[0] < 8:
         raise ValueError(f"{Xte.shape[0]} test rows left after {Ntr} training rows; the report needs 8 (lower --ntr)")
+    levels = ae.noise_schedule(corruption[1], epochs) if corruption else None
     train, reconstruct, encode, decode, theta = ae.ConstructVanillaAE(
-        Xtr, Denc=[hidden], Dz=Dz, Ddec=[hidden], inf=AdaGrad(0.01))
+        Xtr, Denc=[hidden], Dz=Dz, Ddec=[hidden], inf=AdaGrad(0.01),
+        corruption=(corruption[0], levels[0] if levels else 0.0) if corruption else None)
     print('Training the autoencoder.')
     mse = []
     for i in range(epochs):
+        if levels:
+            train.set_noise(levels[i])
         idx = rnd.permutation(np.arange(Ntr)).astype(np.int32)
         mse.extend(train.ctx.train_many(idx, batch_size).tolist())
         print('Epoch ' + str(i) + '. mse = ' + str(mse[-1]))
@@ -77,17 +101,17 @@ def _learn(Xtr, Xte, epochs, Dz, hidden, batch_size=100):
     return recon, encode, decode, Xtr, Xte
 
 
-def LearnFreyFace(epochs=100, Dz=20, Ntr=1500, hidden=FREY["hidden"], data=None, synthetic=False):
+def LearnFreyFace(epochs=100, Dz=20, Ntr=1500, hidden=FREY["hidden"], data=None, synthetic=False, corruption=None):
     """ae.py:129-166.  Returns (reconstruct, encode, decode, Xtr, Xte); reconstruct.train is the
     training function (train.mse(X): the device-side MSE), reconstruct.mse_curve the per-step se / M."""
     Xtr, Xte = data if data is not None else load_frey(Ntr, synthetic)
-    return _learn(Xtr, Xte, epochs, Dz, hidden)
+    return _learn(Xtr, Xte, epochs, Dz, hidden, corruption=corruption)
 
 
-def LearnMNIST(epochs=25, Dz=20, Ntr=50000, hidden=MNIST["hidden"], data=None, synthetic=False):
+def LearnMNIST(epochs=25, Dz=20, Ntr=50000, hidden=MNIST["hidden"], data=None, synthetic=False, corruption=None):
     """ae.py:174-211; returns as LearnFreyFace."""
     Xtr, Xte = data if data is not None else load_mnist(Ntr, synthetic)
-    return _learn(Xtr, Xte, epochs, Dz, hidden)
+    return _learn(Xtr, Xte, epochs, Dz, hidden, corruption=corruption)
 
 
 def _report(data_type, Dz, reconstruct, Xte, out_dir):
@@ -105,7 +129,8 @@ def _report(data_type, Dz, reconstruct, Xte, out_dir):
 def main(argv=None, data=None):
     """ae.py:216-251.  data: {"continuous": (Xtr, Xte), "discrete": (Xtr, Xte)} overrides the files
     (tests).  --epochs overrides every model's epoch count, --hidden both hidden widths, --ntr both
-    training-row counts.  Returns {(data_type, Dz): mse}."""
+    training-row counts, --corruption / --noise make the run a denoising one (checked before any device
+    work).  Returns {(data_type, Dz): mse}."""
     args = list(sys.argv[1:] if argv is None else argv)
     out_dir = get_arg('out', args, 'reconstruction_res', str)
     epochs = get_arg('epochs', args, None, int)
@@ -113,6 +138,8 @@ def main(argv=None, data=None):
     hidden = get_arg('hidden', args, None, int)
     ntr = get_arg('ntr', args, None, int)
     synthetic = get_flag('synthetic', args)
+    corruption = corruption_args(get_arg('corruption', args, None, str),
+                                 get_arg('noise', args, None, lambda s: [float(v) for v in s.split(',')]))
     if args:
         print('Have unused args: {0}'.format(args))
     data = data or {}
@@ -125,11 +152,11 @@ def main(argv=None, data=None):
     for Dz in dz_list:
         reconstruct, _, _, _, Xte = LearnFreyFace(
             epochs=epochs if epochs is not None else frey_epochs(Dz), Dz=Dz, Ntr=ntr or FREY["Ntr"],
-            hidden=hidden or FREY["hidden"], data=data.get('continuous'), synthetic=synthetic)
+            hidden=hidden or FREY["hidden"], data=data.get('continuous'), synthetic=synthetic, corruption=corruption)
         res[('continuous', Dz)] = _report('continuous', Dz, reconstruct, Xte, out_dir)
         reconstruct, _, _, _, Xte = LearnMNIST(
             epochs=epochs if epochs is not None else MNIST["epochs"], Dz=Dz, Ntr=ntr or MNIST["Ntr"],
-            hidden=hidden or MNIST["hidden"], data=data.get('discrete'), synthetic=synthetic)
+            hidden=hidden or MNIST["hidden"], data=data.get('discrete'), synthetic=synthetic, corruption=corruption)
         res[('discrete', Dz)] = _report('discrete', Dz, reconstruct, Xte, out_dir)
     return res
 
