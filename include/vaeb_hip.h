@@ -289,7 +289,7 @@ typedef struct vaeb_ae_config {
     int32_t latent;                       /* enum vaeb_ae_latent (0: the point latent)       */
     int32_t iw_samples;                   /* K of the training objective (below); 0, 1: ELBO */
     int32_t corruption;                   /* enum vaeb_ae_corruption (0: none), offset 112   */
-    int32_t reserved[1];
+    int32_t prior;                        /* enum vaeb_ae_prior (0: N(0, 1)), offset 116     */
 } vaeb_ae_config;
 
 typedef struct vaeb_ae vaeb_ae;
@@ -423,6 +423,51 @@ int vaeb_ae_push_corruption(vaeb_ae* ae, const float* r, int64_t rows);
  * the pushed rows, which must number n).  Changes no parameter, accumulator, step or push; runs in
  * max_batch chunks, so n need not fit max_batch. */
 int vaeb_ae_corrupt(vaeb_ae* ae, const int32_t* idx, int32_t n, float* out);
+
+/* Two-mode latent prior and binary codes (extension): vaeb_ae_config.prior == VAEB_AE_PRIOR_TWO_MODE,
+ * VAEB_AE_LATENT_GAUSS contexts only.  Per latent dimension the N(0, 1) prior is replaced by an
+ * equal-weight mixture of two Gaussians of one width,
+ *   p(z) = 1/2 N(z; 0, s^2) + 1/2 N(z; a, s^2),      a = mean1, s = width, c = 1 / s^2,
+ * which pulls every latent towards {0, a}: a sparsity-inducing prior under which a row is encoded
+ * as Dz bits by truncating the posterior mean.  Per element (row m, latent j):
+ *   t = a (2 z - a) c / 2,   r = sigmoid(t)          (the responsibility of the mode at a)
+ *   log p(z) = -1/2 log 2 pi - log(2 s) - 1/2 c z^2 + softplus(t),   dlog p / dz = -c (z - a r),
+ * softplus(t) = max(t, 0) + log(1 + exp(-|t|)) (t reaches 1e3 at small widths).
+ * The ELBO step (iw_samples 0 or 1).  The KL to a mixture has no closed form, so the prior term is
+ * taken at the step's sample z = mu + exp(lv / 2) eps and the entropy stays analytic:
+ *   latent_row = sum_j [1/2 (1 + lv_j) - log(2 s) - 1/2 c z_j^2 + softplus(t_j)]   (replaces negKL)
+ *   train(idx) returns (loglik + sum_m latent_row) / M,  and with dz the decoder's gradient into z
+ *   g = dz - c (z - a r),   dmu = g,   dlv = 1/2 g (z - mu) + 1/2.
+ * vaeb_ae_elbo sums loglik + latent_row with evaluation noise.
+ * The importance-weighted forms (vaeb_ae_marginal_ll on such a context; training with iw_samples >= 2):
+ *   log w_k = loglik_row(x | z_k) + sum_j [1/2 eps_kj^2 + 1/2 lv_j - log(2 s) - 1/2 c z_kj^2 + softplus(t_kj)]
+ *   u = dz - wn c (z - a r),   dmu_k = u,   dlv_k = 1/2 u (z - mu) + 1/2 wn.
+ * At a = 0, s = 1 the importance-weighted forms are the N(0, 1) context's 1/2 sum (eps^2 + lv - z^2)
+ * and u = dz - wn z (equal up to rounding: the arithmetic differs); the ELBO form is then a
+ * one-sample estimate whose expectation over eps is the analytic negKL, not the same number per step.
+ * Nothing else changes: the theta layout, the noise draws, the Philox keys and the step counter are
+ * those of the N(0, 1) context, as are vaeb_ae_encode, _reconstruct, _decode, _encode_dist and
+ * _sq_error.  Valid with every otype a GAUSS context allows, with iw_samples >= 2 and with every
+ * corruption.  Any other value of `prior`, or TWO_MODE on a POINT or ACT context, is VAEB_ERR_ARG at
+ * create, before the device is touched.  A context of the N(0, 1) prior launches what it launched
+ * before the extension existed.
+ * The four calls below are VAEB_ERR_ARG on a context created with VAEB_AE_PRIOR_NORMAL. */
+enum vaeb_ae_prior { VAEB_AE_PRIOR_NORMAL = 0, VAEB_AE_PRIOR_TWO_MODE = 1 };
+/* mean1 = 1 and width = 0.25 after create.  Valid: finite |mean1| <= 1e3 and 1e-3 <= width <= 1e3
+ * (c and t stay finite in float32 for any sane z); NaN or out of range is VAEB_ERR_ARG with both
+ * values unchanged.  a, c and log(2 s) are passed to the launches by value: no synchronise, and
+ * steps already enqueued keep theirs.  A schedule of falling widths is vaeb_ae_set_prior between
+ * training calls. */
+int vaeb_ae_set_prior(vaeb_ae* ae, float mean1, float width);
+int vaeb_ae_get_prior(vaeb_ae* ae, float* mean1, float* width);
+/* Binary codes.  encode_bits: bit j of row i is mu_ij >= a / 2 (mu = vaeb_ae_encode's output, a
+ * float32 comparison), packed into out_words [n x ceil(Dz / 32)]: bit j at word j / 32, bit j % 32;
+ * the padding bits of a row's last word are 0.  decode_bits: vaeb_ae_decode of z_ij = a where the
+ * bit is set, else 0; out [n x Dobs].  Both run in max_batch chunks (n need not fit max_batch) and
+ * change no parameter, accumulator, step or push.  n <= 0 or a NULL pointer is VAEB_ERR_ARG before
+ * the device is touched. */
+int vaeb_ae_encode_bits(vaeb_ae* ae, const float* x, int64_t n, uint32_t* out_words);
+int vaeb_ae_decode_bits(vaeb_ae* ae, const uint32_t* words, int64_t n, float* out);
 
 #ifdef __cplusplus
 }

@@ -41,6 +41,7 @@ EXPORTS = [
     "vaeb_ae_elbo", "vaeb_ae_marginal_ll", "vaeb_ae_sq_error",
     "vaeb_ae_set_corruption_level", "vaeb_ae_get_corruption_level", "vaeb_ae_set_corruption_noise",
     "vaeb_ae_push_corruption", "vaeb_ae_corrupt",
+    "vaeb_ae_set_prior", "vaeb_ae_get_prior", "vaeb_ae_encode_bits", "vaeb_ae_decode_bits",
 ]
 DIAG_EXPORTS = ["vaeb_profile_steps", "vaeb_kernel_name", "vaeb_debug_timeline", "vaeb_test_gemm_bf16",
                 "vaeb_bench_gemm_bf16", "vaeb_graph_status", "vaeb_comm_info", "vaeb_time_update_many", "vaeb_busy",
@@ -51,6 +52,7 @@ AE_BINARY, AE_CONT, AE_SE = 0, 1, 2
 AE_OTYPE = {"binary": AE_BINARY, "cont": AE_CONT, "se": AE_SE}
 AE_LATENT = {"point": 0, "gauss": 1, "act": 3}   # 2 is unassigned
 AE_CORRUPTION = {"none": 0, "mask": 1, "saltpepper": 2, "gauss": 3}   # enum vaeb_ae_corruption
+AE_PRIOR = {"normal": 0, "twomode": 1}   # enum vaeb_ae_prior
 ACT = {"tanh": 0, "sigmoid": 1, "relu": 2}
 
 
@@ -71,7 +73,7 @@ class AEConfigC(ctypes.Structure):
         ("Dz", ctypes.c_int32), ("n_dec", ctypes.c_int32), ("Ddec", ctypes.c_int32 * 8),
         ("otype", ctypes.c_int32), ("act", ctypes.c_int32), ("s2", ctypes.c_float), ("eta", ctypes.c_float),
         ("max_batch", ctypes.c_int32), ("device", ctypes.c_int32), ("latent", ctypes.c_int32),
-        ("iw_samples", ctypes.c_int32), ("corruption", ctypes.c_int32), ("reserved", ctypes.c_int32 * 1),
+        ("iw_samples", ctypes.c_int32), ("corruption", ctypes.c_int32), ("prior", ctypes.c_int32),
     ]
 
 
@@ -185,9 +187,17 @@ def load():
         "vaeb_ae_set_corruption_noise": ([_P, ctypes.c_int32, ctypes.c_uint64], ctypes.c_int),
         "vaeb_ae_push_corruption": ([_P, _F, _I64], ctypes.c_int),
         "vaeb_ae_corrupt": ([_P, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, _F], ctypes.c_int),
+        "vaeb_ae_set_prior": ([_P, ctypes.c_float, ctypes.c_float], ctypes.c_int),
+        "vaeb_ae_get_prior": ([_P, _F, _F], ctypes.c_int),
+        "vaeb_ae_encode_bits": ([_P, _F, _I64, ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
+        "vaeb_ae_decode_bits": ([_P, ctypes.POINTER(ctypes.c_uint32), _I64, _F], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
-        fn = getattr(lib, name)
+        fn = getattr(lib, name, None)
+        if fn is None and os.environ.get("VAEB_LIB_VARIANT"):
+            continue   # diagnostics A/B: a variant built from an older tree lacks the newer calls
+        if fn is None:
+            raise VaebError(f"{LIB_PATH} does not export {name}")
         fn.argtypes = args
         fn.restype = res
     _lib = lib
@@ -560,10 +570,13 @@ class AEContext:
     latent="act" is the vanilla squared-error autoencoder (vanilla-ae/ae.py): train returns se / n.
     corruption="mask" | "saltpepper" | "gauss": denoising training (enum vaeb_ae_corruption): the
     encoder's first layer reads the rows corrupted at set_corruption_level's level, the output is
-    scored on the clean rows; the evaluation calls never corrupt."""
+    scored on the clean rows; the evaluation calls never corrupt.
+    prior="twomode" (latent="gauss" only; enum vaeb_ae_prior): per latent dimension the prior
+    1/2 N(0, s^2) + 1/2 N(a, s^2) at set_prior's (mean1 a, width s), and the binary codes
+    encode_bits / decode_bits."""
 
     def __init__(self, Dobs, Denc, Dz, Ddec, otype="binary", act="tanh", s2=1.0, eta=0.01, max_batch=100,
-                 device=0, latent="point", iw_samples=1, corruption="none"):
+                 device=0, latent="point", iw_samples=1, corruption="none", prior="normal"):
         self.lib = load()
         c = AEConfigC()
         c.Dobs, c.Dz = int(Dobs), int(Dz)
@@ -590,6 +603,10 @@ class AEContext:
             raise VaebError(f"corruption {corruption!r} not supported (none | mask | saltpepper | gauss)")
         c.corruption = AE_CORRUPTION[corruption]
         self.corruption = corruption
+        if prior not in AE_PRIOR:
+            raise VaebError(f"prior {prior!r} not supported (normal | twomode)")
+        c.prior = AE_PRIOR[prior]
+        self.prior = prior
         self.cfg = c
         self.Dobs, self.Dz = c.Dobs, c.Dz
         self.h = _P()
@@ -736,4 +753,31 @@ class AEContext:
         idx = np.ascontiguousarray(idx, np.int32)
         out = np.empty((idx.size, self.Dobs), np.float32)
         check(self.lib.vaeb_ae_corrupt(self.h, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), idx.size, fptr(out)))
+        return out
+
+    # ---- two-mode latent prior (prior="twomode") ----
+    def set_prior(self, mean1, width):
+        check(self.lib.vaeb_ae_set_prior(self.h, float(mean1), float(width)))
+
+    def get_prior(self):
+        """(mean1, width)."""
+        a, s = ctypes.c_float(), ctypes.c_float()
+        check(self.lib.vaeb_ae_get_prior(self.h, ctypes.byref(a), ctypes.byref(s)))
+        return a.value, s.value
+
+    def encode_bits(self, x):
+        """The binary codes of x [n x Dobs] as uint32 words [n x ceil(Dz / 32)]: bit j of a row
+        (word j // 32, bit j % 32) is encode(x)[j] >= mean1 / 2 (vaeb_ae_encode_bits)."""
+        x = np.ascontiguousarray(x, np.float32)
+        out = np.empty((x.shape[0], -(-self.Dz // 32)), np.uint32)
+        check(self.lib.vaeb_ae_encode_bits(self.h, fptr(x), x.shape[0], out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))))
+        return out
+
+    def decode_bits(self, words):
+        """decode of z = mean1 where the bit is set, else 0, for words [n x ceil(Dz / 32)]
+        (vaeb_ae_decode_bits): [n x Dobs]."""
+        words = np.ascontiguousarray(words, np.uint32).reshape(-1, -(-self.Dz // 32))
+        out = np.empty((words.shape[0], self.Dobs), np.float32)
+        check(self.lib.vaeb_ae_decode_bits(self.h, words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), words.shape[0],
+                                           fptr(out)))
         return out

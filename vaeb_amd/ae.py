@@ -24,6 +24,13 @@ output is scored on the clean rows (include/vaeb_hip.h enum vaeb_ae_corruption):
 autoencoder, and with ConstructVAE the denoising VAE.  train.set_noise(level), train.noise and
 train.corrupt(idx) steer and show the corruption; noise_schedule and train_epochs(noise=...) run a
 schedule of falling levels.
+
+Two-mode latent prior (extension; the report's "Latent space priors" follow-up): ConstructVAE takes
+`prior=` "twomode", ("twomode", width) or ("twomode", mean1, width).  Each latent dimension then has
+the prior 1/2 N(0, width^2) + 1/2 N(mean1, width^2) (include/vaeb_hip.h enum vaeb_ae_prior), which
+pulls the posterior means towards {0, mean1}; train.code(X) truncates them to Dz bits per row and
+train.decode_code(bits) decodes such codes.  train.set_prior(width=...) between epochs runs a schedule
+of falling widths.
 """
 from __future__ import annotations
 
@@ -139,8 +146,62 @@ class _DenoisingTrain:
         return self.ctx.corrupt(np.asarray(idx, np.int32))
 
 
+def _prior(prior):
+    """(mean1, width) of ConstructVAE's prior argument, None for the N(0, 1) prior: None, "twomode",
+    ("twomode", width) or ("twomode", mean1, width)."""
+    if prior is None:
+        return None
+    name, *rest = (prior,) if isinstance(prior, str) else tuple(prior)
+    if name != "twomode" or len(rest) > 2:
+        raise ValueError(f"prior {prior!r} not supported (None | 'twomode' | ('twomode', width) | "
+                         "('twomode', mean1, width))")
+    mean1, width = {0: (1.0, 0.25), 1: (1.0, *rest), 2: tuple(rest)}[len(rest)]
+    return float(mean1), float(width)
+
+
+class _TwoModeTrain:
+    """train(idx) of a context with the two-mode latent prior: the wrapped train function (its
+    attributes included) with the prior of the steps to come (set_prior / prior) and the binary
+    codes (code / decode_code / code_bits_per_row)."""
+
+    def __init__(self, train, ctx):
+        self._train, self.ctx = train, ctx
+        self.code_bits_per_row = ctx.Dz
+
+    def __call__(self, idx):
+        return self._train(idx)
+
+    def __getattr__(self, name):   # only what the instance itself lacks: set_noise, noise, corrupt
+        return getattr(self._train, name)
+
+    def set_prior(self, mean1=None, width=None):
+        a, s = self.ctx.get_prior()
+        self.ctx.set_prior(a if mean1 is None else mean1, s if width is None else width)
+
+    @property
+    def prior(self):
+        """(mean1, width)."""
+        return self.ctx.get_prior()
+
+    def code(self, X):
+        """bool [n x Dz]: encode(X) >= mean1 / 2, the posterior mean truncated to its nearer mode."""
+        words = self.ctx.encode_bits(_values(X))
+        j = np.arange(self.ctx.Dz)
+        return ((words[:, j // 32] >> (j % 32).astype(np.uint32)) & 1).astype(bool)
+
+    def decode_code(self, bits):
+        """The decoder's output [n x Dobs] for codes [n x Dz] (bool or 0 / 1): z = mean1 where set, else 0."""
+        bits = np.asarray(bits)
+        if bits.ndim != 2 or bits.shape[1] != self.ctx.Dz or not np.isin(bits, (0, 1)).all():
+            raise ValueError(f"codes must be a bool or 0 / 1 array [n x {self.ctx.Dz}]")
+        j = np.arange(self.ctx.Dz)
+        words = np.zeros((bits.shape[0], -(-self.ctx.Dz // 32)), np.uint32)
+        np.bitwise_or.at(words, (slice(None), j // 32), bits.astype(np.uint32) << (j % 32).astype(np.uint32))
+        return self.ctx.decode_bits(words)
+
+
 def _construct(latent, Xtr, Denc, Dz, Ddec, f, s2, inf, otype, max_batch, device, iw_samples=1, corruption=None,
-               corruption_seed=0):
+               corruption_seed=0, prior="normal"):
     """The shared body of ConstructAE / ConstructVAE / ConstructVanillaAE; returns (train, ctx, theta),
     train(idx) being one step of the engine on the rows Xtr[idx] with train.ctx = ctx."""
     kind, level = _corruption(corruption)
@@ -156,7 +217,7 @@ def _construct(latent, Xtr, Denc, Dz, Ddec, f, s2, inf, otype, max_batch, device
     K = max(1, int(iw_samples))   # the K sample planes of a step are stacked inside max_batch
     mb = int(max_batch) if max_batch else max(100 * K, min(4096, Xtr.shape[0]))
     ctx = _lib.AEContext(Dobs, Denc, Dz, Ddec, otype=otype, act=_act_name(f), s2=s2, eta=inf.eta, max_batch=mb,
-                         device=device, latent=latent, iw_samples=iw_samples, corruption=kind)
+                         device=device, latent=latent, iw_samples=iw_samples, corruption=kind, prior=prior)
     ctx.set_data(Xtr)
     ctx.set_params(np.concatenate([t.ravel() for t in theta0]))
     offs = np.cumsum([0] + [int(np.prod(s)) for _, s in shapes])
@@ -188,7 +249,7 @@ def ConstructAE(Xtr, Denc=(500,), Dz=20, Ddec=(500,), f="tanh", s2=1.0, inf=None
 
 
 def ConstructVAE(Xtr, Denc=(500,), Dz=20, Ddec=(500,), f="tanh", s2=1.0, inf=None, otype="binary", seed=10,
-                 max_batch=None, device=0, iw_samples=1, corruption=None, corruption_seed=0):
+                 max_batch=None, device=0, iw_samples=1, corruption=None, corruption_seed=0, prior=None):
     """ConstructAE with a Gaussian latent: the same five return values, theta in the order
     [..., Wzmu, Wzlv, bzmu, bzlv, ...].  train(idx) takes one AdaGrad step on the ELBO of the
     rows Xtr[idx] (one Philox draw per row and latent, keyed by `seed`, the dataset row and the
@@ -201,9 +262,19 @@ def ConstructVAE(Xtr, Denc=(500,), Dz=20, Ddec=(500,), f="tanh", s2=1.0, inf=Non
     bound instead (K draws per row, sample stream k) and returns that bound / len(idx); a step needs
     K * len(idx) <= max_batch, which defaults to max(100 K, min(4096, N)).  train.iw_samples is K.
     corruption: the denoising VAE (the encoder sees the corrupted rows, the bound is scored on the clean
-    ones; `corruption_seed` keys the corruption, `seed` the latent noise)."""
+    ones; `corruption_seed` keys the corruption, `seed` the latent noise).
+    prior: "twomode", ("twomode", width) or ("twomode", mean1, width) (defaults 1 and 0.25): the
+    two-mode latent prior of the module docstring, with every iw_samples and corruption.  train(idx)
+    then returns (loglik + latent_row) / len(idx), the prior term taken at the step's sample, and
+    train gains set_prior(mean1=None, width=None), prior, code(X), decode_code(bits) and
+    code_bits_per_row (= Dz).  None: the N(0, 1) prior, with theta_0, context and steps as ever."""
+    two = _prior(prior)   # raises before a context is made
     train, ctx, theta = _construct("gauss", Xtr, Denc, Dz, Ddec, f, s2, inf, otype, max_batch, device, iw_samples,
-                                   corruption=corruption, corruption_seed=corruption_seed)
+                                   corruption=corruption, corruption_seed=corruption_seed,
+                                   prior="twomode" if two else "normal")
+    if two:
+        ctx.set_prior(*two)
+        train = _TwoModeTrain(train, ctx)
     ctx.set_eps_mode(_lib.EPS_PHILOX, seed)
     train.iw_samples = ctx.iw_samples
     train.elbo = lambda X: ctx.elbo(_values(X))

@@ -37,7 +37,7 @@ struct AeIwArgs {
     const float* eps_in;   // the pushed eps [n * K][Dz]
     const float *mu, *lv;  // [R][Dz]
     float* z;              // [S * R][Dz]
-    float* lat;            // [S * R] latent term 1/2 sum_j (eps^2 + lv - z^2)
+    float* lat;            // [S * R] latent term 1/2 sum_j (eps^2 + lv - z^2) (two-mode prior: below)
     int* yrow;             // [S * R] the row of the chunk's x each stacked row observes
     const int* idx;        // training form: the dataset rows [R] of the step (c0 and yrow), the
                            // training domain k << 1, row0 = the step's offset in the call's idx
@@ -47,7 +47,11 @@ struct AeIwArgs {
 // One 16-lane group per (plane, row): lane li takes the latents li, li + 16, ...  No pad
 // rows: the layer-stack kernels bound-check rows themselves.  Grid: ceil(S * R / 16)
 // workgroups of 256.
-__global__ __launch_bounds__(256) void ae_iw_sample_kernel(AeIwArgs a) {
+// The body is shared by the kernel of the N(0, 1) prior and that of the two-mode prior (TM,
+// ae_mlp.hpp AePriorArgs: lat = sum_j [1/2 eps^2 + 1/2 lv + log p(z) + 1/2 log 2 pi]); the prior's
+// arguments exist in the latter alone.
+template <bool TM>
+DEV void ae_iw_sample_body(const AeIwArgs& a, const AePriorArgs<TM>& pr) {
     const int li = threadIdx.x & 15;
     const int g = blockIdx.x * 16 + (threadIdx.x >> 4);
     if (g >= a.S * a.R) return;   // whole 16-lane groups leave; sum16 stays inside a group
@@ -67,13 +71,18 @@ __global__ __launch_bounds__(256) void ae_iw_sample_kernel(AeIwArgs a) {
         const float e = erow ? erow[j] : philox_normal(a.seed, c0, (uint32_t)j, c23);
         const float z = mu + fexp(0.5f * lv) * e;
         zrow[j] = z;
-        t += e * e + lv - z * z;
+        if constexpr (TM) t += 0.5f * (e * e + lv) + pr.logp(z);
+        else t += e * e + lv - z * z;
     }
     t = sum16(t);
     if (li == 0) {
-        a.lat[g] = 0.5f * t;
+        a.lat[g] = TM ? t : 0.5f * t;
         a.yrow[g] = xrow;
     }
+}
+__global__ __launch_bounds__(256) void ae_iw_sample_kernel(AeIwArgs a) { ae_iw_sample_body<false>(a, AePriorArgs<false>{}); }
+__global__ __launch_bounds__(256) void ae_iw_sample_tm_kernel(AeIwArgs a, AePriorArgs<true> pr) {
+    ae_iw_sample_body<true>(a, pr);
 }
 
 struct AeIwWeightArgs {

@@ -25,6 +25,17 @@
 //                         rows, output deltas scaled by the normalised weights wn, then
 //                         dmu_k = dz - wn z, dlv_k = 1/2 (dz - wn z)(z - mu) + 1/2 wn
 //                                                               PAeBwdT<true> (mode LATENT_IW)
+//   two-mode latent prior (VAEB_AE_PRIOR_TWO_MODE, Gaussian latent only): per latent dimension
+//                         p(z) = 1/2 N(z; 0, s^2) + 1/2 N(z; a, s^2); with c = 1 / s^2,
+//                         t = a (2 z - a) c / 2, r = sigmoid(t),
+//                         log p(z) = -1/2 log 2 pi - log(2 s) - 1/2 c z^2 + softplus(t),
+//                         dlog p / dz = -c (z - a r).  The KL has no closed form: the latent
+//                         partials are 1/2 (1 + lv) - log(2 s) - 1/2 c z^2 + softplus(t) at the
+//                         step's z                          PAeFwdT<false, true> (mode LATENT)
+//                         g = dz - c (z - a r), dmu = g, dlv = 1/2 g (z - mu) + 1/2
+//                                                           PAeBwdT<false, true> (mode LATENT)
+//                         u = dz - wn c (z - a r), dmu_k = u, dlv_k = 1/2 u (z - mu) + 1/2 wn
+//                                                           PAeBwdT<true, true> (mode LATENT_IW)
 //   weight gradients:     [in | 1]^T dout (ones row = bias gradient), prior -theta/s2 and
 //                         AdaGrad (infalg.py:155-161) in the epilogue   PAeWgrad
 // The first layer's A operand is gathered on the fly through idx (no copy of Xtr[idx]).
@@ -66,8 +77,28 @@ DEV float el(rsrc_t b, int ld, int r, int k, int rlim, int klim) {
 // delta 2 (Y - P) P (1 - P) in dA and P in out; Y with dA == nullptr: the partials only, as the
 // other output modes.  The branch exists only in PAeFwdT<true> (the kernel arguments are the
 // same), so PAeFwd's kernels are what they were without it.
-template <bool SE>
-struct PAeFwdT {
+//
+// The two-mode latent prior (TM): a = mean1, c = 1 / width^2 and log(2 width), by value.  The
+// three arguments and the branches that read them exist only in the TM instantiations of
+// PAeFwdT and PAeBwdT (an empty base otherwise), so every other kernel and its arguments are what
+// they were without them.  t = a (2 z - a) c / 2; softplus in its max(t, 0) + log(1 + e^-|t|)
+// form (t reaches 1e3 at small widths: e^t is inf in float32) and r = sigmoid(t) from the same
+// e^-|t|.
+template <bool TM> struct AePriorArgs {};
+template <> struct AePriorArgs<true> {
+    float pa, pc, plog2s;
+    DEV float t_of(float z) const { return 0.5f * pa * (2.f * z - pa) * pc; }
+    // log p(z) + 1/2 log 2 pi
+    DEV float logp(float z) const { return softplusf(t_of(z)) - plog2s - 0.5f * pc * z * z; }
+    // -dlog p / dz = c (z - a r)
+    DEV float pull(float z) const {
+        const float t = t_of(z), e = fexp(-fabsf(t)), q = frcp(1.f + e);
+        return pc * (z - pa * (t >= 0.f ? q : e * q));
+    }
+};
+
+template <bool SE, bool TM = false>
+struct PAeFwdT : AePriorArgs<TM> {
     Dbg a;
     int M, N, K;
     const float* in; int ldin; int in_rows; const int* idx;   // idx: gathered input rows
@@ -128,6 +159,17 @@ struct PAeFwdT {
                         e = philox_normal(seed, m < M ? (erow ? (uint32_t)erow[m] : erow0 + (uint32_t)m) : 0u,
                                           (uint32_t)n, philox_c23(step, domain));
                     const float sd = fexp(0.5f * lv);
+                    if constexpr (TM) {   // the prior term at the sample z, the entropy analytic
+                        const float z = (noise == NOISE_ZERO) ? v : v + sd * e;
+                        if (ok) {
+                            out[(int64_t)m * N + n] = v;
+                            out2[(int64_t)m * N + n] = lv;
+                            zout[(int64_t)m * N + n] = z;
+                        }
+                        const float s = sum16(ok ? 0.5f * (1.f + lv) + this->logp(z) : 0.f);
+                        if ((lane & 15) == 0 && m < M) llpart[(int64_t)m * nct + n0 / 16] = s;
+                        continue;
+                    }
                     if (ok) {
                         out[(int64_t)m * N + n] = v;
                         out2[(int64_t)m * N + n] = lv;
@@ -190,6 +232,7 @@ struct PAeFwdT {
 
 using PAeFwd = PAeFwdT<false>;
 using PAeFwdSe = PAeFwdT<true>;
+using PAeFwdTm = PAeFwdT<false, true>;   // F_LATENT under the two-mode prior (2 heads)
 
 // ---------------------------------------------------------------- backward (data) layer
 // din[M x N] = [dout | dout2] [W | W2]^T  (K = K1 or 2 K1), then * f'(h) or - h (Z prior).
@@ -201,10 +244,12 @@ using PAeFwdSe = PAeFwdT<true>;
 // (no analytic KL: the latent term of log w is differentiated as it stands).  The branch and its
 // two arguments exist only in PAeBwdT<true>, so PAeBwd's kernels and kernel arguments are what
 // they were without it.
+// Two-mode prior (TM, AePriorArgs above): B_LATENT g = dz - c (z - a r), din = g,
+// din2 = 1/2 g (z - mu) + 1/2 (lv is not read); B_LATENT_IW u = dz - wn c (z - a r).
 template <bool IW> struct AeBwdIwArgs {};
 template <> struct AeBwdIwArgs<true> { const float* wt; int Mp; };   // wn [M], rows per sample plane
-template <bool IW>
-struct PAeBwdT : AeBwdIwArgs<IW> {
+template <bool IW, bool TM = false>
+struct PAeBwdT : AeBwdIwArgs<IW>, AePriorArgs<TM> {
     Dbg a;
     int M, N, K;
     const float *dout, *dout2; int K1;
@@ -257,13 +302,24 @@ struct PAeBwdT : AeBwdIwArgs<IW> {
                 if (mode == B_LATENT_IW) {
                     const int64_t o = (int64_t)m * N + n, om = (int64_t)(m % this->Mp) * N + n;
                     const float w = this->wt[m], z = h3[o], mu = h[om];
-                    const float u = acc[0][r] - w * z;
+                    float u;
+                    if constexpr (TM) u = acc[0][r] - w * this->pull(z);
+                    else u = acc[0][r] - w * z;
                     din[o] = u;
                     din2[o] = 0.5f * u * (z - mu) + 0.5f * w;
                     continue;
                 }
             }
             const float hv = h[(int64_t)m * N + n];
+            if constexpr (TM) {
+                if (mode == B_LATENT) {
+                    const float z = h3[(int64_t)m * N + n];
+                    const float g = acc[0][r] - this->pull(z);
+                    din[(int64_t)m * N + n] = g;
+                    din2[(int64_t)m * N + n] = 0.5f * g * (z - hv) + 0.5f;
+                    continue;
+                }
+            }
             if (mode == B_LATENT) {
                 const float dz = acc[0][r], lv = h2[(int64_t)m * N + n], z = h3[(int64_t)m * N + n];
                 din[(int64_t)m * N + n] = dz - hv;

@@ -16,6 +16,11 @@
 //                         ae_elbo_kernel | ae_sum_to_host
 //   vaeb_ae_marginal_ll   ae_chunks: ae_encode (zero noise), per pass of sample planes ae_iw_sample_kernel |
 //                         ae_decode_hidden | ae_output(VALUE) | iw_lse_kernel, then ae_sum_to_host
+//   vaeb_ae_encode_bits   ae_chunks: ae_encode (zero noise) | ae_pack_bits_kernel
+//   vaeb_ae_decode_bits   ae_chunks: ae_unpack_bits_kernel | ae_decode_hidden | ae_output(PREDICT)
+// A context of the two-mode latent prior (c.prior, ae_two_mode) runs the same sequences with the TM
+// instantiations of the latent forward, the decoder's first-layer backward and the sample kernel;
+// every other context launches what it launched before.
 // vaeb_ae_create lays theta out (an AeLayer per layer and head); device memory is the context's:
 // vaeb_ae::mem (dev_owner.hpp) registers every buffer where it is allocated, vaeb_ae_destroy releases it.
 
@@ -70,6 +75,10 @@ struct vaeb_ae {
     uint64_t cor_seed = 0;
     float* cor_in = nullptr;
     int64_t cor_rows = 0, cor_cap = 0;
+    // the two-mode latent prior (c.prior == VAEB_AE_PRIOR_TWO_MODE): mean1 and width, launch
+    // arguments as the level above; a chunk's code words [max_batch x ceil(Dz / 32)] (first use)
+    float pr_mean1 = 1.f, pr_width = 0.25f;
+    uint32_t* code_w = nullptr;
 };
 
 namespace {
@@ -78,6 +87,15 @@ bool ae_gauss(const vaeb_ae* a) { return a->c.latent == VAEB_AE_LATENT_GAUSS; }
 bool ae_act_latent(const vaeb_ae* a) { return a->c.latent == VAEB_AE_LATENT_ACT; }
 bool ae_iw(const vaeb_ae* a) { return a->c.iw_samples >= 2; }
 bool ae_corrupting(const vaeb_ae* a) { return a->c.corruption != VAEB_AE_CORRUPT_NONE; }
+bool ae_two_mode(const vaeb_ae* a) { return a->c.prior == VAEB_AE_PRIOR_TWO_MODE; }
+
+// The prior's launch arguments a, c = 1 / s^2 and log(2 s) into a TM parameter block (nothing
+// into any other: the overload is chosen by the block's base).
+void ae_put_prior(const vaeb_ae*, ae::AePriorArgs<false>&) {}
+void ae_put_prior(const vaeb_ae* a, ae::AePriorArgs<true>& q) {
+    const double s = a->pr_width;
+    q.pa = a->pr_mean1; q.pc = (float)(1.0 / (s * s)); q.plog2s = (float)std::log(2.0 * s);
+}
 
 // vaeb_ae_marginal_ll's and the importance-weighted step's scratch, sized by max_batch
 int ae_iw_scratch(vaeb_ae* a) {
@@ -158,18 +176,23 @@ int ae_encode(vaeb_ae* a, const AeRows& x, int M, const AeNoise& nz) {
     const AeRows h{a->H[ne], M};
     if (!ae_gauss(a))   // Z = H Wz + bz, or f of it (the activated latent)
         return ae_fwd_layer(a, a->lat.l[0], h, M, ae_act_latent(a) ? ae::F_ACT : ae::F_LINEAR, a->Z);
-    ae::PAeFwd p = ae_fwd_args<ae::PAeFwd>(a, a->lat.l[0], h, M);
-    p.W2 = a->theta + a->lat.l[1].oW; p.b2 = a->theta + a->lat.l[1].ob;
-    p.mode = ae::F_LATENT; p.out = a->mu; p.out2 = a->lv; p.zout = a->Z;
-    p.llpart = a->kl; p.nct = cdiv(a->c.Dz, 16);
-    p.seed = a->seed;
-    if (nz.kind != AE_EPS_ZERO && a->eps_mode == VAEB_EPS_HOST) {
-        p.noise = ae::NOISE_HOST; p.eps_in = a->eps_in + nz.r0 * a->c.Dz;
-    } else if (nz.kind != AE_EPS_ZERO) {
-        p.noise = ae::NOISE_PHILOX; p.erow = nz.rows; p.erow0 = (uint32_t)nz.r0;
-        p.step = a->step; p.domain = nz.kind == AE_EPS_EVAL ? 1u : 0u;
-    }
-    launch_bigk<2>(a->s, p);
+    auto latent = [&](auto p) {   // two-mode prior: kl holds the latent_row partials at z
+        p = ae_fwd_args<decltype(p)>(a, a->lat.l[0], h, M);
+        p.W2 = a->theta + a->lat.l[1].oW; p.b2 = a->theta + a->lat.l[1].ob;
+        p.mode = ae::F_LATENT; p.out = a->mu; p.out2 = a->lv; p.zout = a->Z;
+        p.llpart = a->kl; p.nct = cdiv(a->c.Dz, 16);
+        p.seed = a->seed;
+        if (nz.kind != AE_EPS_ZERO && a->eps_mode == VAEB_EPS_HOST) {
+            p.noise = ae::NOISE_HOST; p.eps_in = a->eps_in + nz.r0 * a->c.Dz;
+        } else if (nz.kind != AE_EPS_ZERO) {
+            p.noise = ae::NOISE_PHILOX; p.erow = nz.rows; p.erow0 = (uint32_t)nz.r0;
+            p.step = a->step; p.domain = nz.kind == AE_EPS_EVAL ? 1u : 0u;
+        }
+        ae_put_prior(a, p);
+        launch_bigk<2>(a->s, p);
+    };
+    if (ae_two_mode(a)) latent(ae::PAeFwdTm{});
+    else latent(ae::PAeFwd{});
     CHECK_LAUNCH();
     return 0;
 }
@@ -239,10 +262,10 @@ int ae_wgrad(vaeb_ae* a, const AeLayer& l, const AeRows& in, const float* dout, 
 // old weights (din == nullptr: none, no data gradient into x), followed by each head's update.
 // This order is load-bearing (ae_mlp.hpp: every weight is updated only after the last kernel of
 // the step that reads it), and it exists here only.
-template <bool IW = false>
+template <bool IW = false, bool TM = false>
 int ae_bwd_layer(vaeb_ae* a, const AeLayer* l, float* const* d, int nh, const AeRows& in, int M, int mode, float* din) {
     if (din) {
-        ae::PAeBwdT<IW> p{};
+        ae::PAeBwdT<IW, TM> p{};
         p.M = M; p.N = l[0].K; p.K = nh * l[0].N;
         p.dout = d[0]; p.K1 = l[0].N; p.W = a->theta + l[0].oW;
         if (nh == 2) { p.dout2 = d[1]; p.W2 = a->theta + l[1].oW; }
@@ -251,6 +274,7 @@ int ae_bwd_layer(vaeb_ae* a, const AeLayer* l, float* const* d, int nh, const Ae
             p.h = a->mu; p.h2 = a->lv; p.h3 = a->Z; p.din = a->dmu; p.din2 = a->dlv;
         }
         if constexpr (IW) { p.wt = a->iw_wt; p.Mp = M / a->c.iw_samples; }
+        ae_put_prior(a, p);
         launch_bigk<1>(a->s, p);
         CHECK_LAUNCH();
     }
@@ -261,13 +285,17 @@ int ae_bwd_layer(vaeb_ae* a, const AeLayer* l, float* const* d, int nh, const Ae
 
 // Output layer and decoder (top down) over R rows; dG[i+1] is the pre-activation delta of layer i.
 // mode0 is the first decoder layer's: B_ZPRIOR (dZ = dz - Z), B_DACT (the activated latent: times
-// f'(Z), no - Z), B_LATENT (dmu, dlv) or B_LATENT_IW (dmu_k, dlv_k per stacked row).
+// f'(Z), no - Z), B_LATENT (dmu, dlv) or B_LATENT_IW (dmu_k, dlv_k per stacked row); the latter two
+// in their TM instantiations on a context of the two-mode prior.
 int ae_bwd_decoder(vaeb_ae* a, int R, int mode0) {
     const int nd = a->c.n_dec, act = ae::B_DACT;
     if (int rc = ae_bwd_layer(a, a->out.l, a->out.d, a->out.n, AeRows{a->G[nd], R}, R, act, a->dG[nd])) return rc;
     for (int i = nd - 1; i > 0; --i)
         if (int rc = ae_bwd_layer(a, &a->dec[i], &a->dG[i + 1], 1, AeRows{a->G[i], R}, R, act, a->dG[i])) return rc;
     const AeRows z{a->Z, R};
+    if (ae_two_mode(a))
+        return mode0 == ae::B_LATENT_IW ? ae_bwd_layer<true, true>(a, a->dec, &a->dG[1], 1, z, R, mode0, a->dZ)
+                                        : ae_bwd_layer<false, true>(a, a->dec, &a->dG[1], 1, z, R, mode0, a->dZ);
     return mode0 == ae::B_LATENT_IW ? ae_bwd_layer<true>(a, a->dec, &a->dG[1], 1, z, R, mode0, a->dZ)
                                     : ae_bwd_layer(a, a->dec, &a->dG[1], 1, z, R, mode0, a->dZ);
 }
@@ -281,6 +309,19 @@ int ae_bwd_encoder(vaeb_ae* a, const AeRows& x, int M) {
     for (int i = ne - 1; i > 0; --i)
         if (int rc = ae_bwd_layer(a, &a->enc[i], &a->dH[i + 1], 1, AeRows{a->H[i], M}, M, act, a->dH[i])) return rc;
     return ae_bwd_layer(a, a->enc, &a->dH[1], 1, x, M, act, nullptr);
+}
+
+// z, the latent terms and the gather list of `rows` stacked rows (ae_iwae.hpp), under the context's prior.
+int ae_iw_sample(vaeb_ae* a, const ae::AeIwArgs& q, int rows) {
+    if (ae_two_mode(a)) {
+        ae::AePriorArgs<true> pr{};
+        ae_put_prior(a, pr);
+        hipLaunchKernelGGL(ae::ae_iw_sample_tm_kernel, dim3(cdiv(rows, 16)), dim3(256), 0, a->s, q, pr);
+    } else {
+        hipLaunchKernelGGL(ae::ae_iw_sample_kernel, dim3(cdiv(rows, 16)), dim3(256), 0, a->s, q);
+    }
+    CHECK_LAUNCH();
+    return 0;
 }
 
 // The forward of a step on the K-sample importance-weighted bound (c.iw_samples = K >= 2,
@@ -298,8 +339,7 @@ int ae_iw_forward(vaeb_ae* a, const AeRows& xe, const AeRows& x, int M, int slot
     q.eps_mode = a->eps_mode == VAEB_EPS_HOST ? 1 : 0;
     q.seed = a->seed; q.step = a->step; q.eps_in = a->eps_in;
     q.mu = a->mu; q.lv = a->lv; q.z = a->Z; q.lat = a->iw; q.yrow = a->iw_yrow; q.idx = x.idx;
-    hipLaunchKernelGGL(ae::ae_iw_sample_kernel, dim3(cdiv(KM, 16)), dim3(256), 0, a->s, q);
-    CHECK_LAUNCH();
+    if (int rc = ae_iw_sample(a, q, KM)) return rc;
     if (int rc = ae_decode_hidden(a, a->Z, KM)) return rc;
     if (int rc = ae_output(a, KM, AE_OUT_TRAIN, AeRows{x.p, x.rows, a->iw_yrow})) return rc;
     ae::AeIwWeightArgs w{};
@@ -457,6 +497,10 @@ int vaeb_ae_create(const vaeb_ae_config* cfg, vaeb_ae** out) {
     if (g.corruption < VAEB_AE_CORRUPT_NONE || g.corruption > VAEB_AE_CORRUPT_GAUSS)
         return fail(VAEB_ERR_ARG, "corruption must be VAEB_AE_CORRUPT_NONE | _MASK | _SALT_PEPPER | _GAUSS (got %d)",
                     g.corruption);
+    if (g.prior != VAEB_AE_PRIOR_NORMAL && g.prior != VAEB_AE_PRIOR_TWO_MODE)
+        return fail(VAEB_ERR_ARG, "prior must be VAEB_AE_PRIOR_NORMAL | _TWO_MODE (got %d)", g.prior);
+    if (g.prior == VAEB_AE_PRIOR_TWO_MODE && g.latent != VAEB_AE_LATENT_GAUSS)
+        return fail(VAEB_ERR_ARG, "prior VAEB_AE_PRIOR_TWO_MODE needs a VAEB_AE_LATENT_GAUSS context");
     if (g.corruption != VAEB_AE_CORRUPT_NONE && g.Dobs >= (1 << 30))
         return fail(VAEB_ERR_ARG, "corruption needs Dobs < 2^30 (the Philox c1 field)");
     if (g.corruption != VAEB_AE_CORRUPT_NONE && (int64_t)g.max_batch * g.Dobs >= (1 << 29))
@@ -725,8 +769,7 @@ int vaeb_ae_marginal_ll(vaeb_ae* a, const float* x, int64_t n, int32_t K, double
             for (int k0 = 0; k0 < K; k0 += smax) {
                 const int S = std::min(smax, K - k0);
                 w.k0 = q.k0 = k0; w.S = q.S = S;
-                hipLaunchKernelGGL(ae::ae_iw_sample_kernel, dim3(cdiv(S * R, 16)), dim3(256), 0, a->s, q);
-                CHECK_LAUNCH();
+                if (int rc = ae_iw_sample(a, q, S * R)) return rc;
                 if (int rc = ae_decode_hidden(a, a->Z, S * R)) return rc;
                 if (int rc = ae_output(a, S * R, AE_OUT_VALUE, AeRows{a->xin, R, a->iw_yrow})) return rc;
                 hipLaunchKernelGGL(iw_lse_kernel, dim3(cdiv(R, 256)), dim3(256), 0, a->s, w);
@@ -739,6 +782,67 @@ int vaeb_ae_marginal_ll(vaeb_ae* a, const float* x, int64_t n, int32_t K, double
 }
 #undef AE_NEED_GAUSS
 #undef AE_NEED_STEP
+
+// ------------------------------------------------------------------ two-mode latent prior
+#define AE_NEED_TWO_MODE(a, fn)                                                                         \
+    do {                                                                                                \
+        if (!(a)) return fail(VAEB_ERR_ARG, "null argument");                                           \
+        if (!ae_two_mode(a)) return fail(VAEB_ERR_ARG, fn " needs a context created with VAEB_AE_PRIOR_TWO_MODE"); \
+    } while (0)
+
+int vaeb_ae_set_prior(vaeb_ae* a, float mean1, float width) {
+    AE_NEED_TWO_MODE(a, "vaeb_ae_set_prior");
+    if (!(std::fabs(mean1) <= 1e3f) || !(width >= 1e-3f && width <= 1e3f))   // NaN fails both
+        return fail(VAEB_ERR_ARG, "prior mean1 %g, width %g: |mean1| <= 1e3 and 1e-3 <= width <= 1e3", (double)mean1,
+                    (double)width);
+    a->pr_mean1 = mean1; a->pr_width = width;   // launch arguments: the enqueued steps keep theirs
+    return 0;
+}
+
+int vaeb_ae_get_prior(vaeb_ae* a, float* mean1, float* width) {
+    AE_NEED_TWO_MODE(a, "vaeb_ae_get_prior");
+    if (!mean1 || !width) return fail(VAEB_ERR_ARG, "null argument");
+    *mean1 = a->pr_mean1; *width = a->pr_width;
+    return 0;
+}
+
+int vaeb_ae_encode_bits(vaeb_ae* a, const float* x, int64_t n, uint32_t* out_words) {
+    AE_NEED_TWO_MODE(a, "vaeb_ae_encode_bits");
+    if (!x || !out_words || n <= 0) return fail(VAEB_ERR_ARG, "bad arguments");
+    const vaeb_ae_config& g = a->c;
+    const int nw = cdiv(g.Dz, 32);
+    if (int rc = a->mem.lazy(&a->code_w, (int64_t)g.max_batch * nw)) return rc;
+    return ae_chunks(a, x, n, g.Dobs, [&](int64_t r0, int rows) {
+        if (int rc = ae_encode(a, AeRows{a->xin, rows}, rows, AeNoise{})) return rc;   // vaeb_ae_encode's mu
+        hipLaunchKernelGGL(ae::ae_pack_bits_kernel, dim3(cdiv(rows * nw, 256)), dim3(256), 0, a->s, a->mu, rows, g.Dz,
+                           0.5f * a->pr_mean1, a->code_w);
+        CHECK_LAUNCH();
+        HIP_TRY(hipMemcpyAsync(out_words + r0 * nw, a->code_w, sizeof(uint32_t) * (size_t)rows * nw,
+                               hipMemcpyDeviceToHost, a->s));
+        HIP_TRY(hipStreamSynchronize(a->s));
+        return 0;
+    });
+}
+
+int vaeb_ae_decode_bits(vaeb_ae* a, const uint32_t* words, int64_t n, float* out) {
+    AE_NEED_TWO_MODE(a, "vaeb_ae_decode_bits");
+    if (!words || !out || n <= 0) return fail(VAEB_ERR_ARG, "bad arguments");
+    const vaeb_ae_config& g = a->c;
+    const int nw = cdiv(g.Dz, 32);
+    // the chunk loop uploads 4-byte elements, whatever they hold: nw words per row into xin (>= Dz per row)
+    return ae_chunks(a, reinterpret_cast<const float*>(words), n, nw, [&](int64_t r0, int rows) {
+        hipLaunchKernelGGL(ae::ae_unpack_bits_kernel, dim3(cdiv(rows * g.Dz, 256)), dim3(256), 0, a->s,
+                           reinterpret_cast<const uint32_t*>(a->xin), rows, g.Dz, a->pr_mean1, a->Z);
+        CHECK_LAUNCH();
+        if (int rc = ae_decode_hidden(a, a->Z, rows)) return rc;   // vaeb_ae_decode's launches on z in {0, a}
+        if (int rc = ae_output(a, rows, AE_OUT_PREDICT)) return rc;
+        HIP_TRY(hipMemcpyAsync(out + r0 * g.Dobs, a->Xpr, sizeof(float) * (size_t)rows * g.Dobs, hipMemcpyDeviceToHost,
+                               a->s));
+        HIP_TRY(hipStreamSynchronize(a->s));
+        return 0;
+    });
+}
+#undef AE_NEED_TWO_MODE
 
 // ------------------------------------------------------------------ input corruption
 int vaeb_ae_set_corruption_level(vaeb_ae* a, float level) {

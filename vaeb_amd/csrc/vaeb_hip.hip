@@ -46,6 +46,7 @@
 #include "ae_mlp.hpp"
 #include "ae_iwae.hpp"
 #include "ae_corrupt.hpp"
+#include "ae_codes.hpp"
 
 using namespace vaeb;
 
@@ -577,7 +578,7 @@ const char* vaeb_last_error(void) { return g_err.c_str(); }
 
 int vaeb_version(int32_t* major, int32_t* minor) {
     if (major) *major = 0;
-    if (minor) *minor = 3;
+    if (minor) *minor = 4;
     return 0;
 }
 
