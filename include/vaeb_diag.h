@@ -83,6 +83,34 @@ int vaeb_dp_rank_update(vaeb_ctx* ctx, int32_t world, int32_t rank, int32_t buck
 /* Diagnostics (bf16 engine): the current bf16 shadow of the weight elements, in arena
  * (reference) order; n = the number of weight elements (the arena before the biases). */
 int vaeb_get_shadow(vaeb_ctx* ctx, uint16_t* out, int64_t n);
+/* Diagnostics (16-bit engine, bf16 or fp16 per the context's dtype): the buffers of the last
+ * training step as the kernels left them.  vaeb_get_h16 copies the first n raw 16-bit words of a
+ * named buffer, vaeb_get_h16_f32 the first n floats of one of the step's fp32 latent buffers, after
+ * a stream synchronise; nothing else is launched and a context that never calls them does what it
+ * does without them.  VAEB_ERR_ARG: unknown name, or n past the buffer's capacity;
+ * VAEB_ERR_STATE: an fp32 context.  B = the batch, L the samples per row, R = the context's row
+ * capacity (max(B, max_eval_rows) rounded up to 16); every buffer is row-major with its leading
+ * dimension equal to its width (no pad columns), and a step writes rows [0, L B) (or [0, B)) only:
+ * the GEMMs that read a buffer see it through a view of exactly those rows (engine_bf16.inc
+ * bf_mats), past which the buffer descriptor returns 0, so rows up to the capacity are never read.
+ *   vaeb_get_h16      rows x ld      capacity   contents
+ *     "h"             B x H          R H        tanh(X W3 + b3)
+ *     "z"             L B x Z        R L Z      plane l at rows [l B, (l + 1) B): mu + exp(lv / 2) eps_l
+ *     "hd"            L B x H        R L H      tanh(z W1 + b1)
+ *     "dA"            L B x Dn       R L Dn     Bernoulli (Dn = D): dA2 = sl (x - y).  Gaussian (Dn = 2 D):
+ *                                               [dA2 | dA6] interleaved in 32-column groups, data column d of
+ *                                               dA2 at column 64 (d / 32) + d % 32, of dA6 32 further (the
+ *                                               shadow's [W2 | W6] rule, h16_common.hpp ShadowMap s26)
+ *     "dA1"           L B x H        R L H      (dA [W2 | W6]^T) (1 - hd^2)
+ *     "dml"           B x 2 Z        R 2 Z      [dMu | dLv]: dMu at columns [0, Z), dLv at [Z, 2 Z)
+ *     "dA3"           B x H          R H        (dml [W4 | W5]^T) (1 - h^2)
+ *   vaeb_get_h16_f32: "mu", "lv" B x Z (capacity R Z); "eps" L B x Z (R L Z), the noise the step used.
+ * sl = sc / L, sc = 1 (sum objective) or 1 / B_global (mean objective).  Loss scale: an fp16 context
+ * with the mean objective stores dA, dA1, dml and dA3 multiplied by S = the largest power of two
+ * <= B_global (engine_bf16.inc h16_scale; the weight- and bias-gradient epilogues multiply by 1 / S);
+ * S = 1 for bf16 and for the sum objective.  h, z and hd are never scaled. */
+int vaeb_get_h16(vaeb_ctx* ctx, const char* name, uint16_t* out, int64_t n);
+int vaeb_get_h16_f32(vaeb_ctx* ctx, const char* name, float* out, int64_t n);
 /* Diagnostics: one eager step with a 100 MHz s_memrealtime stamp per workgroup at the
  * stage boundaries of every launch; out = [launch][1024 workgroups][8 slots]. */
 int vaeb_debug_timeline(vaeb_ctx* ctx, int32_t batch_index, uint64_t* out, int64_t cap,

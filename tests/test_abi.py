@@ -52,7 +52,8 @@ def test_diagnostics_are_not_in_the_dropin_header():
     """The drop-in boundary (vaeb_hip.h) holds only the reference's operations and their
     state transfers; timing / GEMM test hooks live in vaeb_diag.h."""
     pub = header_functions()
-    for f in ("vaeb_debug_timeline", "vaeb_test_gemm_bf16", "vaeb_bench_gemm_bf16", "vaeb_profile_steps"):
+    for f in ("vaeb_debug_timeline", "vaeb_test_gemm_bf16", "vaeb_bench_gemm_bf16", "vaeb_profile_steps", "vaeb_get_h16",
+              "vaeb_get_h16_f32"):
         assert f not in pub and f in header_functions(DIAG_HEADER)
 
 

@@ -45,7 +45,8 @@ EXPORTS = [
 ]
 DIAG_EXPORTS = ["vaeb_profile_steps", "vaeb_kernel_name", "vaeb_debug_timeline", "vaeb_test_gemm_bf16",
                 "vaeb_bench_gemm_bf16", "vaeb_graph_status", "vaeb_comm_info", "vaeb_time_update_many", "vaeb_busy",
-                "vaeb_dp_plan", "vaeb_dp_rank_update", "vaeb_get_shadow", "vaeb_dw2_plan"]
+                "vaeb_dp_plan", "vaeb_dp_rank_update", "vaeb_get_shadow", "vaeb_dw2_plan", "vaeb_get_h16",
+                "vaeb_get_h16_f32"]
 GRAPH_MODES = {0: "off", 1: "not_captured", 2: "replay", 3: "eager_fallback"}
 AE_MAX_LAYERS = 8
 AE_BINARY, AE_CONT, AE_SE = 0, 1, 2
@@ -154,6 +155,8 @@ def load():
         "vaeb_dw2_plan": ([ctypes.POINTER(VaebConfig)] + [ctypes.POINTER(ctypes.c_int32)] * 6 + [ctypes.c_int32],
                           ctypes.c_int),
         "vaeb_get_shadow": ([_P, ctypes.POINTER(ctypes.c_uint16), _I64], ctypes.c_int),
+        "vaeb_get_h16": ([_P, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint16), _I64], ctypes.c_int),
+        "vaeb_get_h16_f32": ([_P, ctypes.c_char_p, _F, _I64], ctypes.c_int),
         "vaeb_time_update_many": ([_P, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, _F,
                                    ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
         "vaeb_debug_timeline": ([_P, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64), _I64,
@@ -521,6 +524,18 @@ class Context:
         uint16 bits."""
         out = np.empty(int(n_weights), np.uint16)
         check(self.lib.vaeb_get_shadow(self.h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)), out.size))
+        return out
+
+    def get_h16(self, name, n):
+        """Diagnostics (16-bit engine): the first n elements of a buffer of the last training step
+        (include/vaeb_diag.h vaeb_get_h16): "h", "z", "hd", "dA", "dA1", "dml", "dA3" as raw uint16
+        bits (bf16 or fp16 per the context's dtype); "mu", "lv", "eps" as float32."""
+        if name in ("mu", "lv", "eps"):
+            out = np.empty(int(n), np.float32)
+            check(self.lib.vaeb_get_h16_f32(self.h, name.encode(), fptr(out), out.size))
+            return out
+        out = np.empty(int(n), np.uint16)
+        check(self.lib.vaeb_get_h16(self.h, name.encode(), out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)), out.size))
         return out
 
     def bench_gemm_bf16(self, a_kouter, b_kouter, M, N, K, tile_n=0, reps=10):

@@ -85,6 +85,14 @@ typedef _Float16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 bf16x2_t __attribute__((ext_vector_type(2)));
 DEV uint32_t f2bf(float f) { return __builtin_bit_cast(uint16_t, (_Float16)f); }
 DEV float bf2f(uint32_t b) { return (float)__builtin_bit_cast(_Float16, (uint16_t)b); }
+// f2bf of a value that is ALSO stored as fp32 (theta' and its shadow): the 16-bit copy must be the
+// rounding of the stored value.  Without the barrier hipcc folds the fp32 FMA that produced f into
+// the conversion (v_fma_mixlo_f16: the exact FMA rounded once, to fp16), which is not Q(fp32 value)
+// where that value sits on an fp16 rounding tie (the mean objective's decay term makes theta' an FMA).
+DEV uint32_t f2bf_of_stored(float f) {
+    asm volatile("" : "+v"(f));
+    return f2bf(f);
+}
 DEV f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
 // The range guard of the backward's and z's 16-bit stores (h16_engines.hpp H16_CHECK / H16_REPORT):
 // a lane that converted a value outside +-65504 (or NaN / inf) sets kStF16Range in the control
@@ -103,9 +111,18 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 DEV uint32_t f2bf(float f) { return __builtin_bit_cast(uint16_t, (__bf16)f); }
 DEV float bf2f(uint32_t b) { return __builtin_bit_cast(float, b << 16); }
+DEV uint32_t f2bf_of_stored(float f) { return f2bf(f); }   // (fp16: see above; no mixed-precision FMA writes bf16)
 DEV f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 #endif
 DEV uint32_t f2bf2(float a, float b) { return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2_t){a, b}, bf16x2_t)); }
+#if VAEB_H16_F16
+DEV uint32_t f2bf2_of_stored(float a, float b) {   // f2bf_of_stored, two values
+    asm volatile("" : "+v"(a), "+v"(b));
+    return f2bf2(a, b);
+}
+#else
+DEV uint32_t f2bf2_of_stored(float a, float b) { return f2bf2(a, b); }
+#endif
 // Epilogue functors with a post(m0, n0, smem) step after store_out (kPost; gemm8_body only)
 template <class E, class = void> struct HasPost : std::false_type {};
 template <class E> struct HasPost<E, std::void_t<decltype(E::kPost)>> : std::bool_constant<E::kPost> {};
@@ -1008,7 +1025,7 @@ struct Opt {
         const float tn = th + lr * gg / (__builtin_amdgcn_sqrtf(a) + eps) - decay * th * th;
         accum[idx] = a;
         th_out[idx] = tn;
-        if (sidx >= 0) shadow_out[sidx] = (bf16_t)f2bf(tn);
+        if (sidx >= 0) shadow_out[sidx] = (bf16_t)f2bf_of_stored(tn);
     }
 };
 
@@ -1067,7 +1084,7 @@ struct EpiAdagrad {
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, a), bac, off[u], 0, 0);
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, tn), bto, off[u], 0, 0);
                 if (so[u] >= 0)
-                    *reinterpret_cast<uint2*>(opt.shadow_out + so[u]) = make_uint2(f2bf2(tn[0], tn[1]), f2bf2(tn[2], tn[3]));
+                    *reinterpret_cast<uint2*>(opt.shadow_out + so[u]) = make_uint2(f2bf2_of_stored(tn[0], tn[1]), f2bf2_of_stored(tn[2], tn[3]));
             }
         }
     }
@@ -1114,7 +1131,7 @@ struct EpiAdagrad {
                                          opt.decay * th[j][r] * th[j][r];
                         bst(bac, off[j][r], a);
                         bst(bto, off[j][r], tn);
-                        if (off[j][r] != kOOB) opt.shadow_out[(int64_t)row * (sld ? sld : N) + col] = (bf16_t)f2bf(tn);
+                        if (off[j][r] != kOOB) opt.shadow_out[(int64_t)row * (sld ? sld : N) + col] = (bf16_t)f2bf_of_stored(tn);
                     }
                 }
         }

@@ -589,7 +589,7 @@ __global__ __launch_bounds__(256) void adagrad_bf16_kernel(Opt o, int64_t P, DpR
             bst(bac, off[u], a);
             bst(bto, off[u], tn);
             const int64_t si = m.at(i);
-            if (si >= 0) o.shadow_out[si] = (bf16_t)f2bf(tn);
+            if (si >= 0) o.shadow_out[si] = (bf16_t)f2bf_of_stored(tn);
         }
     }
     if (r.book && blockIdx.x == 0 && threadIdx.x == 0) {

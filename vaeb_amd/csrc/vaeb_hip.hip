@@ -1675,6 +1675,42 @@ int vaeb_get_shadow(vaeb_ctx* c, uint16_t* out, int64_t n) {
     return 0;
 }
 
+// The 16-bit step's buffers by name: a device pointer and its capacity in elements (include/vaeb_diag.h).
+static int h16_copy_out(vaeb_ctx* c, const char* what, const char* name, const void* src, int64_t cap, size_t elem,
+                        void* out, int64_t n) {
+    if (!src) return fail(VAEB_ERR_STATE, "%s: buffer %s not allocated", what, name);
+    if (n < 0 || n > cap)
+        return fail(VAEB_ERR_ARG, "%s: buffer %s holds %lld elements, %lld requested", what, name, (long long)cap, (long long)n);
+    HIP_TRY(hipStreamSynchronize(c->s));   // (a forked step has joined its second stream into c->s)
+    HIP_TRY(hipMemcpy(out, src, elem * (size_t)n, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int vaeb_get_h16(vaeb_ctx* c, const char* name, uint16_t* out, int64_t n) {
+    if (!c || !name || !out) return fail(VAEB_ERR_ARG, "null argument");
+    if (!is_bf16(c)) return fail(VAEB_ERR_STATE, "vaeb_get_h16: only a 16-bit context keeps 16-bit step buffers");
+    const bf::BfState& b = c->bf;
+    const int64_t R = c->cap, RL = (int64_t)c->cap * c->c.L, H = c->c.H, Z = c->c.Z;
+    const struct { const char* name; const uint16_t* p; int64_t cap; } bufs[] = {
+        {"h", b.h, R * H}, {"z", b.z, RL * Z}, {"hd", b.hd, RL * H}, {"dA", b.dA, RL * b.Dn},
+        {"dA1", b.dA1, RL * H}, {"dml", b.dml, R * 2 * Z}, {"dA3", b.dA3, R * H}};
+    for (auto& e : bufs)
+        if (strcmp(e.name, name) == 0) return h16_copy_out(c, "vaeb_get_h16", name, e.p, e.cap, sizeof(uint16_t), out, n);
+    return fail(VAEB_ERR_ARG, "vaeb_get_h16: unknown buffer '%s'", name);
+}
+
+int vaeb_get_h16_f32(vaeb_ctx* c, const char* name, float* out, int64_t n) {
+    if (!c || !name || !out) return fail(VAEB_ERR_ARG, "null argument");
+    if (!is_bf16(c)) return fail(VAEB_ERR_STATE, "vaeb_get_h16_f32: only a 16-bit context keeps 16-bit step buffers");
+    const bf::BfState& b = c->bf;
+    const int64_t R = c->cap, RL = (int64_t)c->cap * c->c.L, Z = c->c.Z;
+    const struct { const char* name; const float* p; int64_t cap; } bufs[] = {
+        {"mu", b.mu, R * Z}, {"lv", b.lv, R * Z}, {"eps", b.eps, RL * Z}};
+    for (auto& e : bufs)
+        if (strcmp(e.name, name) == 0) return h16_copy_out(c, "vaeb_get_h16_f32", name, e.p, e.cap, sizeof(float), out, n);
+    return fail(VAEB_ERR_ARG, "vaeb_get_h16_f32: unknown buffer '%s'", name);
+}
+
 int vaeb_kernel_name(int32_t id, char* out, int32_t cap) {
     if (!out || cap <= 0) return fail(VAEB_ERR_ARG, "bad buffer");
     const int n = (int)(sizeof(kKernelNames) / sizeof(kKernelNames[0]));
