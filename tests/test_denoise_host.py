@@ -1,6 +1,6 @@
 """Host checks (no GPU) of the layer-stack engine's denoising training (include/vaeb_hip.h
 enum vaeb_ae_corruption): the oracle the GPU tests compare against (tests/denoise_oracle.py) is
-pinned to the existing oracles and to float64 torch autograd, the GPU cases' inputs are shown to sit
+pinned to float64 torch autograd for every latent and output type, the GPU cases' inputs are shown to sit
 inside their caps in float32, to tell a mis-keyed draw apart and to show the two wirings most likely
 to be got wrong (the output scored on the corrupted rows; the first layer's gradient taken from the
 clean rows), the counter layout is shown to be disjoint from every other draw, and the ABI and Python
@@ -20,7 +20,6 @@ from oracle import ae_oracle as A
 from oracle import philox
 from tests import denoise_oracle as D
 from tests import vae_stack_oracle as V
-from tests import vanilla_ae_oracle as N
 from tests.test_gpu_ae import check_theta
 from tests.test_vae_stack_host import (ACC_RTOL, PHILOX_B, SEED, STEP, STEP_CASES, VALUE_RTOL, philox_setup,
                                        step_setup)
@@ -121,38 +120,7 @@ def philox_case(draw=None):
     return Case(cfg, "gauss", PHILOX_KIND, PHILOX_LEVEL, 1, X, params, acc, idx, eps, r if draw is None else draw)
 
 
-# ------------------------------------------------------------------ 1. Xin is Y: the existing oracles
-PIN_KW = dict(Dobs=37, Denc=(29, 17), Dz=5, Ddec=(13, 21), s2=2.0)
-
-
-@pytest.mark.parametrize("latent,otype", [("point", "binary"), ("point", "cont"), ("point", "se"), ("act", "binary"),
-                                          ("act", "cont"), ("act", "se"), ("gauss", "binary"), ("gauss", "cont")])
-def test_clean_input_is_the_existing_oracle_exactly(latent, otype):
-    cfg = A.AEConfig(otype=otype, **PIN_KW)
-    rng = np.random.default_rng(4)
-    X = rng.beta(2.0, 2.0, size=(23, cfg.Dobs))
-    params = [(p * 30).astype(np.float64) for p in D.init_params(cfg, latent, seed=3)]
-    eps = rng.standard_normal((23, cfg.Dz))
-    out = D.forward_backward(params, X, X, cfg, latent, eps if latent == "gauss" else None)
-    refs = []
-    if latent == "gauss":
-        ref = V.forward_backward(params, X, eps, cfg)
-        refs.append((ref["elbo"], ref["grads"]))
-        assert out["data"] == ref["loglik"] and out["negkl"] == ref["negkl"] and out["f"] == ref["f"]
-    else:
-        ref = N.forward_backward(params, X, cfg, latent)
-        refs.append((ref["value"], ref["grads"]))
-        assert out["f"] == ref["logjoint"]
-        if latent == "point" and otype != "se":
-            ref = A.forward_backward(params, X, cfg)
-            refs.append((ref["loglik"], ref["grads"]))
-    for value, grads in refs:
-        assert out["value"] == value
-        for n, g, r in zip(D.names(cfg, latent), out["grads"], grads):
-            assert np.array_equal(g, r), n
-
-
-# ------------------------------------------------------------------ 2. Xin != Y: autograd
+# ------------------------------------------------------------------ 1. Xin != Y: autograd
 def torch_objective(tp, Xin, Y, eps, cfg, latent):
     import torch
     act = {"tanh": torch.tanh, "sigmoid": torch.sigmoid, "relu": torch.relu}[cfg.act]
@@ -186,11 +154,22 @@ def torch_objective(tp, Xin, Y, eps, cfg, latent):
     return data + extra + prior
 
 
-@pytest.mark.parametrize("latent,kw", [
-    ("gauss", dict(Dobs=37, Denc=(29, 17), Dz=5, Ddec=(13, 21), otype="binary", s2=2.0)),
+ODD_KW = dict(Dobs=37, Denc=(29, 17), Dz=5, Ddec=(13, 21), s2=2.0)
+# every valid (latent, otype) pair: this is where each is held to autograd with Xin != Y
+AUTOGRAD = [
+    ("gauss", dict(ODD_KW, otype="binary")),
     ("point", dict(Dobs=48, Denc=(20,), Dz=20, Ddec=(18, 11), otype="cont", act="sigmoid")),
     ("act", dict(Dobs=64, Denc=(32,), Dz=16, Ddec=(32,), otype="se")),
-], ids=["gauss-binary-odd", "point-cont", "act-se"])
+    ("gauss", dict(ODD_KW, otype="cont", act="sigmoid")),
+    ("point", dict(ODD_KW, otype="binary", act="relu")),
+    ("point", dict(ODD_KW, otype="se")),
+    ("act", dict(ODD_KW, otype="binary", act="sigmoid")),
+    ("act", dict(ODD_KW, otype="cont", act="relu")),
+]
+
+
+@pytest.mark.parametrize("latent,kw", AUTOGRAD, ids=["gauss-binary-odd", "point-cont", "act-se", "gauss-cont", "point-binary",
+                                                     "point-se", "act-binary", "act-cont"])
 def test_gradient_with_a_separate_encoder_input_matches_autograd(latent, kw):
     import torch
     cfg = A.AEConfig(**kw)

@@ -77,17 +77,6 @@ def test_oracle_gradient_matches_autograd(latent, otype, act):
         assert np.allclose(g, t.grad.numpy(), rtol=1e-9, atol=1e-11)
 
 
-def test_point_latent_is_the_degenerate_vae_oracle():
-    """latent point with a degenerate-vae output is oracle/ae_oracle.py, element for element."""
-    cfg = A.AEConfig(Dobs=20, Denc=(9,), Dz=5, Ddec=(8,), otype="cont", act="sigmoid")
-    rng = np.random.default_rng(1)
-    params = [(0.3 * rng.standard_normal(s)) for _, s in A.param_shapes(cfg)]
-    X = rng.random((6, cfg.Dobs))
-    a, b = A.forward_backward(params, X, cfg), VA.forward_backward(params, X, cfg, "point")
-    assert a["loglik"] == b["value"] and a["logjoint"] == b["logjoint"]
-    assert all(np.array_equal(x, y) for x, y in zip(a["grads"], b["grads"]))
-
-
 # ------------------------------------------------------------------ 2. the known value
 def test_train_step_value_is_se_per_row_and_mse_matches():
     cfg = A.AEConfig(Dobs=12, Denc=(7,), Dz=3, Ddec=(5,), otype="se")

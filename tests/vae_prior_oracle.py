@@ -1,7 +1,7 @@
 """NumPy oracle of the layer-stack engine's two-mode latent prior (include/vaeb_hip.h enum
-vaeb_ae_prior, vaeb_amd/csrc/ae_mlp.hpp AePriorArgs) -- TEST HELPER ONLY, on top of
-tests/vae_stack_oracle.py (parameters, noise keys) and tests/vae_stack_iwtrain_oracle.py (the stacked
-sample planes), which it imports and leaves as they are.
+vaeb_ae_prior, vaeb_amd/csrc/ae_mlp.hpp AePriorArgs) -- TEST HELPER ONLY: oracle.ae_oracle.forward_backward
+with prior = (mean1, width), the parameters and noise keys of tests/vae_stack_oracle.py and
+tests/vae_stack_iwtrain_oracle.py.
 
 Per latent dimension  p(z) = 1/2 N(z; 0, s^2) + 1/2 N(z; a, s^2),  c = 1 / s^2:
 
@@ -20,11 +20,12 @@ float32 values the ABI carries; c and log(2 s) are formed from them in double an
 dtype of the run, as the host does for the launches.  The dtype of the computation is that of the
 parameters (float64: the reference; float32: the restatement that sizes the GPU tests' bounds).
 """
-import math
+import functools
 
 import numpy as np
 
 from oracle import ae_oracle as A
+from oracle.ae_oracle import abi_prior, stable_sigmoid as sigmoid  # noqa: F401
 from tests import vae_stack_iwtrain_oracle as T
 from tests import vae_stack_oracle as V
 
@@ -35,36 +36,42 @@ FORMS = ("elbo", "iw")
 WRONG = ("r_dropped", "a_ignored", "c_on_z_alone", "half_not_half_wn", "naive_softplus")
 
 
-def abi_prior(mean1, width):
-    """(a, s) as the float32 values vaeb_ae_set_prior receives, in double."""
-    return float(np.float32(mean1)), float(np.float32(width))
-
-
 def softplus(t, naive=False):
     if naive:
         with np.errstate(over="ignore"):
             return np.log(1 + np.exp(t))
-    return np.maximum(t, 0) + np.log(1 + np.exp(-np.abs(t)))
-
-
-def sigmoid(t):
-    e = np.exp(-np.abs(t))
-    q = 1 / (1 + e)
-    return np.where(t >= 0, q, e * q)
+    return A.softplus(t)
 
 
 def prior_terms(z, mean1, width, wrong=None):
-    """t, r, log p(z) + 1/2 log 2 pi and the pull c (z - a r) = -dlog p / dz, in z's dtype."""
-    dt = z.dtype
-    a64, s64 = abi_prior(mean1, width)
-    a, c, log2s = dt.type(a64), dt.type(1.0 / (s64 * s64)), dt.type(math.log(2.0 * s64))
-    half = dt.type(0.5)
-    av = dt.type(0) if wrong == "a_ignored" else a
-    t = half * av * (2 * z - av) * c
-    r = np.ones_like(z) if wrong == "r_dropped" else sigmoid(t)
-    logp = softplus(t, naive=wrong == "naive_softplus") - log2s - half * c * z * z
-    pull = c * z - av * r if wrong == "c_on_z_alone" else c * (z - av * r)
+    """oracle.ae_oracle.prior_terms (t, r, log p(z) + 1/2 log 2 pi, the pull c (z - a r)), with one
+    thing wrong in it."""
+    if wrong == "a_ignored":
+        return A.prior_terms(z, 0.0, width)
+    t, r, logp, pull = A.prior_terms(z, mean1, width)
+    a, c, log2s = A.prior_constants(z.dtype, mean1, width)
+    if wrong == "r_dropped":
+        r = np.ones_like(z)
+        pull = c * (z - a * r)
+    elif wrong == "naive_softplus":
+        logp = softplus(t, naive=True) - log2s - z.dtype.type(0.5) * c * z * z
+    elif wrong == "c_on_z_alone":
+        pull = c * z - a * r
     return t, r, logp, pull
+
+
+def _half_not_half_wn(f, dG):
+    K, M, Dz = f.K, f.M, f.cfg.Dz
+    u = dG - f.ws * f.pull
+    dlv_k = f.half * u * (f.Z - np.tile(f.mu, (K, 1))) + f.half
+    return [("Wzmu", u.reshape(K, M, Dz).sum(0)), ("Wzlv", dlv_k.reshape(K, M, Dz).sum(0))]
+
+
+def substituted(wrong):
+    """The steps of the sweep that `wrong` replaces."""
+    if wrong == "half_not_half_wn":
+        return dict(latent_deltas=_half_not_half_wn)
+    return dict(prior_terms=functools.partial(prior_terms, wrong=wrong))
 
 
 def forward_backward(params, X, eps, cfg, mean1, width, form, need_grad=True, Y=None, wrong=None):
@@ -72,96 +79,11 @@ def forward_backward(params, X, eps, cfg, mean1, width, form, need_grad=True, Y=
     of value + NormalPrior(theta, s2) in theta order.  Y: the observations scored (default X: a
     corrupting step passes the clean rows as Y and the corrupted ones as X)."""
     assert form in FORMS and (wrong is None or wrong in WRONG)
-    nm = V.names(cfg)
-    p = dict(zip(nm, params))
-    dt = params[0].dtype
-    X, eps = np.asarray(X, dt), np.asarray(eps, dt)
-    Y = X if Y is None else np.asarray(Y, dt)
-    if form == "elbo":
-        assert eps.ndim == 2
-        eps = eps[None]
-    K, M, Dz = eps.shape
-    ne, nd = len(cfg.Denc), len(cfg.Ddec)
-    half = dt.type(0.5)
-    H = [X]
-    for i in range(ne):
-        H.append(A._act(cfg.act, H[-1] @ p[f"Wenc{i}"] + p[f"benc{i}"]))
-    mu = H[-1] @ p["Wzmu"] + p["bzmu"]
-    lv = H[-1] @ p["Wzlv"] + p["bzlv"]
-    z = mu[None] + np.exp(lv * half)[None] * eps                   # [K, M, Dz]
-    Zs = z.reshape(K * M, Dz)                                      # stacked row g = k M + m
-    Ys = np.tile(Y, (K, 1))
-    G = [Zs]
-    for i in range(nd):
-        G.append(A._act(cfg.act, G[-1] @ p[f"Wdec{i}"] + p[f"bdec{i}"]))
-    e7 = dt.type(A.EPS_LOG)
-    if cfg.otype == "binary":
-        P = 1.0 / (1.0 + np.exp(-(G[-1] @ p["Wout"] + p["bout"])))
-        ll = (Ys * np.log(P + e7) + (1 - Ys) * np.log(1 - P + e7)).sum(1)
-        Xpr = P
-    else:
-        xm = 1.0 / (1.0 + np.exp(-(G[-1] @ p["Wmu"] + p["bmu"])))
-        ls2 = G[-1] @ p["Wlogs2"] + p["blogs2"]
-        rr = Ys - xm
-        ll = (-0.5 * (A.LOG2PI + ls2 + rr * rr / np.exp(ls2))).sum(1)
-        Xpr = xm
-    t, r, logp, pull = prior_terms(z, mean1, width, wrong)
-    out = dict(mu=mu, lv=lv, z=z, t=t, r=r, Xpr=Xpr, H=H, G=G)
-    if form == "elbo":
-        latent = float((half * (1 + lv) + logp[0]).sum(dtype=np.float64))
-        loglik = float(ll.sum(dtype=np.float64))
-        value = loglik + latent
-        wn = np.ones((1, M), dt)
-        out.update(loglik=loglik, latent=latent)
-    else:
-        lat = (half * (eps * eps + lv[None]) + logp).sum(2)        # [K, M]
-        lw = (ll.reshape(K, M) + lat).astype(dt)
-        mx = lw.max(0)
-        e = np.exp(lw - mx)
-        s = e.sum(0)
-        rows = mx + np.log(s) - np.log(dt.type(K))
-        wn = e / s
-        value = float(rows.sum(dtype=np.float64))
-        out.update(rows=rows, lw=lw, lat=lat)
-    s2 = cfg.s2
-    logprior = -0.5 * sum(float((q.astype(np.float64) ** 2 / s2 + math.log(2 * math.pi * s2)).sum()) for q in params)
-    out.update(value=value, wn=wn, f=value + logprior)
-    if not need_grad:
-        return out
-
-    ws = wn.reshape(K * M, 1).astype(dt)
-    g = {}
-    if cfg.otype == "binary":
-        dP = Ys / (P + e7) - (1 - Ys) / (1 - P + e7)
-        dA = dP * P * (1 - P) * ws
-        g["Wout"], g["bout"] = G[-1].T @ dA, dA.sum(0)
-        dG = dA @ p["Wout"].T
-    else:
-        ex = np.exp(-ls2)
-        dAmu = rr * ex * xm * (1 - xm) * ws
-        dAls = (-0.5 + 0.5 * rr * rr * ex) * ws
-        g["Wmu"], g["bmu"] = G[-1].T @ dAmu, dAmu.sum(0)
-        g["Wlogs2"], g["blogs2"] = G[-1].T @ dAls, dAls.sum(0)
-        dG = dAmu @ p["Wmu"].T + dAls @ p["Wlogs2"].T
-    for i in reversed(range(nd)):
-        dPre = dG * A._dact(cfg.act, G[i + 1])
-        g[f"Wdec{i}"], g[f"bdec{i}"] = G[i].T @ dPre, dPre.sum(0)
-        dG = dPre @ p[f"Wdec{i}"].T
-    u = dG - ws * pull.reshape(K * M, Dz)                          # dz - wn c (z - a r)
-    dmu_k = u
-    dlv_k = half * u * (Zs - np.tile(mu, (K, 1))) + (half if wrong == "half_not_half_wn" else half * ws)
-    dmu = dmu_k.reshape(K, M, Dz).sum(0)                           # ascending k
-    dlv = dlv_k.reshape(K, M, Dz).sum(0)
-    g["Wzmu"], g["bzmu"] = H[-1].T @ dmu, dmu.sum(0)
-    g["Wzlv"], g["bzlv"] = H[-1].T @ dlv, dlv.sum(0)
-    dH = dmu @ p["Wzmu"].T + dlv @ p["Wzlv"].T
-    for i in reversed(range(ne)):
-        dPre = dH * A._dact(cfg.act, H[i + 1])
-        g[f"Wenc{i}"], g[f"benc{i}"] = H[i].T @ dPre, dPre.sum(0)
-        if i > 0:
-            dH = dPre @ p[f"Wenc{i}"].T
-    out["data_grads"] = [np.asarray(g[n]).astype(dt) for n in nm]
-    out["grads"] = [(g[n] - p[n] / s2).astype(dt) for n in nm]
+    assert np.ndim(eps) == (2 if form == "elbo" else 3)
+    out = A.forward_backward(params, X, cfg, need_grad, latent="gauss", Y=Y, eps=eps, prior=(mean1, width),
+                             steps=wrong and substituted(wrong))
+    for k in ("z", "t", "r"):                                      # the ELBO form's one plane
+        out[k] = out[k].reshape((-1,) + out[k].shape[-2:])
     return out
 
 

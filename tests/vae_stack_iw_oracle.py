@@ -1,7 +1,8 @@
 """NumPy oracle of the layer-stack engine's importance-weighted bound (include/vaeb_hip.h
 vaeb_ae_marginal_ll, vaeb_amd/csrc/ae_iwae.hpp) -- TEST HELPER ONLY.
 
-Per row of X and sample k, on top of tests/vae_stack_oracle.py's forward pass fed eps[k]:
+Per row of X and sample k, on top of tests/vae_stack_oracle.py's forward pass fed eps[k] (one
+M-row forward per sample, as the device evaluates; its per-row log-likelihood is the forward's "ll"):
 
     log w_k = loglik_row(x | z_k) + 1/2 sum_j (eps_kj^2 + lv_j - z_kj^2)
     IW_K(x) = logsumexp_k log w_k - log K
@@ -14,20 +15,6 @@ from oracle import ae_oracle as A
 from tests import vae_stack_oracle as V
 
 
-def loglik_rows(out, params, X, cfg):
-    """[n]: the output layer's log-likelihood per row, from a V.forward_backward result."""
-    dt = params[0].dtype
-    X = np.asarray(X, dt)
-    if cfg.otype == "binary":
-        P = out["Xpr"]
-        e = dt.type(A.EPS_LOG)
-        return (X * np.log(P + e) + (1 - X) * np.log(1 - P + e)).sum(1)
-    p = dict(zip(V.names(cfg), params))
-    ls2 = out["G"][-1] @ p["Wlogs2"] + p["blogs2"]
-    r = X - out["Xpr"]
-    return (-0.5 * (A.LOG2PI + ls2 + r * r / np.exp(ls2))).sum(1)
-
-
 def log_weights(params, X, eps, cfg):
     """eps [K, n, Dz] -> dict of lw, ll, lat (each [K, n]), the forward results per sample
     (outs) and mu, lv [n, Dz]."""
@@ -37,7 +24,7 @@ def log_weights(params, X, eps, cfg):
     for e in eps:
         out = V.forward_backward(params, X, e, cfg, need_grad=False)
         z, lv = out["z"], out["lv"]
-        ll.append(loglik_rows(out, params, X, cfg))
+        ll.append(out["ll"])
         lat.append(dt.type(0.5) * (e * e + lv - z * z).sum(1))
         outs.append(out)
     ll, lat = np.stack(ll), np.stack(lat)
@@ -46,8 +33,7 @@ def log_weights(params, X, eps, cfg):
 
 def iw_from_lw(lw):
     """[n]: max-subtracted logsumexp over the K samples minus log K, in lw's dtype."""
-    m = lw.max(0)
-    return m + np.log(np.exp(lw - m).sum(0)) - np.log(lw.dtype.type(lw.shape[0]))
+    return A.logsumexp_rows(lw)[0]
 
 
 def iw_rows(params, X, eps, cfg):
