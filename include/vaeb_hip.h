@@ -469,6 +469,42 @@ int vaeb_ae_get_prior(vaeb_ae* ae, float* mean1, float* width);
 int vaeb_ae_encode_bits(vaeb_ae* ae, const float* x, int64_t n, uint32_t* out_words);
 int vaeb_ae_decode_bits(vaeb_ae* ae, const uint32_t* words, int64_t n, float* out);
 
+/* The update rule of the layer-stack engine (extension beyond AdaGrad; the reference's other two
+ * optimisers, infalg.py:44-137, and Adam).  Every rule ASCENDS f with g = df/dtheta (the prior's
+ * -theta / s2 included) in the weight-gradient launch's epilogue; a step launches the same kernels
+ * in the same order whatever the rule.  Per element, with state slots s0 and s1 laid out as theta:
+ *   ADAGRAD   s0' = s0 + g^2;  theta += eta g / (sqrt(s0') + 1e-6)
+ *   SGA       s0' = beta1 s0 + g;  theta += eta s0'          (beta1: the momentum mu in [0, 1);
+ *             at mu = 0 slot 0 after a step IS that step's gradient)
+ *   ADADELTA  s0' = rho s0 + (1 - rho) g^2;  dx = sqrt(s1 + eps) g / sqrt(s0' + eps);
+ *             theta += eta dx;  s1' = rho s1 + (1 - rho) dx^2   (beta1: rho in (0, 1); s0 = g_ac,
+ *             s1 = dx_ac; eta = 1 is the reference's rule)
+ *   ADAM      s0' = beta1 s0 + (1 - beta1) g;  s1' = beta2 s1 + (1 - beta2) g^2;
+ *             theta += eta (s0' / (1 - beta1^t)) / (sqrt(s1' / (1 - beta2^t)) + eps)
+ *             (t: the optimiser step counter below after this step, 1 for the first)
+ * A fresh context is {ADAGRAD, cfg.eta, 0, 0, 1e-6} and steps exactly as it did before this call
+ * existed.  vaeb_ae_set_optimizer with ANOTHER rule zeroes both slots and the step counter (on the
+ * context's stream, after the steps already enqueued); with the SAME rule it changes the
+ * hyper-parameters only -- a step-size schedule between train calls, for AdaGrad too.  They are
+ * launch arguments: steps already enqueued keep theirs.  VAEB_ERR_ARG: an unknown rule; eta <= 0;
+ * a beta outside [0, 1) (rho outside (0, 1)); eps <= 0 for ADADELTA / ADAM; ADAGRAD with eps other
+ * than 1e-6f (its kernel keeps the literal); a field the rule does not use set non-zero (ADAGRAD:
+ * beta1, beta2; SGA: beta2, eps; ADADELTA: beta2).
+ * State: slot 0 is also vaeb_ae_set / get_adagrad_state's array; slot 1 exists for ADADELTA and
+ * ADAM only (VAEB_ERR_ARG otherwise, as n != num_params).  The optimiser step counter advances by
+ * one per training step under every rule; it is not the Philox step counter. */
+enum vaeb_ae_rule { VAEB_AE_RULE_ADAGRAD = 0, VAEB_AE_RULE_SGA = 1, VAEB_AE_RULE_ADADELTA = 2, VAEB_AE_RULE_ADAM = 3 };
+typedef struct vaeb_ae_optimizer {
+    int32_t rule;                         /* enum vaeb_ae_rule                               */
+    float eta, beta1, beta2, eps;
+} vaeb_ae_optimizer;                      /* 20 bytes                                        */
+int vaeb_ae_set_optimizer(vaeb_ae* ae, const vaeb_ae_optimizer* opt);
+int vaeb_ae_get_optimizer(vaeb_ae* ae, vaeb_ae_optimizer* out);
+int vaeb_ae_set_opt_state(vaeb_ae* ae, int32_t slot, const float* flat, int64_t n);
+int vaeb_ae_get_opt_state(vaeb_ae* ae, int32_t slot, float* flat, int64_t n);
+int vaeb_ae_set_opt_step(vaeb_ae* ae, int64_t t);
+int vaeb_ae_get_opt_step(vaeb_ae* ae, int64_t* t);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,6 +42,8 @@ EXPORTS = [
     "vaeb_ae_set_corruption_level", "vaeb_ae_get_corruption_level", "vaeb_ae_set_corruption_noise",
     "vaeb_ae_push_corruption", "vaeb_ae_corrupt",
     "vaeb_ae_set_prior", "vaeb_ae_get_prior", "vaeb_ae_encode_bits", "vaeb_ae_decode_bits",
+    "vaeb_ae_set_optimizer", "vaeb_ae_get_optimizer", "vaeb_ae_set_opt_state", "vaeb_ae_get_opt_state",
+    "vaeb_ae_set_opt_step", "vaeb_ae_get_opt_step",
 ]
 DIAG_EXPORTS = ["vaeb_profile_steps", "vaeb_kernel_name", "vaeb_debug_timeline", "vaeb_test_gemm_bf16",
                 "vaeb_bench_gemm_bf16", "vaeb_graph_status", "vaeb_comm_info", "vaeb_time_update_many", "vaeb_busy",
@@ -54,7 +56,11 @@ AE_OTYPE = {"binary": AE_BINARY, "cont": AE_CONT, "se": AE_SE}
 AE_LATENT = {"point": 0, "gauss": 1, "act": 3}   # 2 is unassigned
 AE_CORRUPTION = {"none": 0, "mask": 1, "saltpepper": 2, "gauss": 3}   # enum vaeb_ae_corruption
 AE_PRIOR = {"normal": 0, "twomode": 1}   # enum vaeb_ae_prior
-ACT = {"tanh": 0, "sigmoid": 1, "relu": 2}
+AE_RULE = {"adagrad": 0, "sga": 1, "adadelta": 2, "adam": 3}   # enum vaeb_ae_rule
+AE_RULE_NAME = {v: k for k, v in AE_RULE.items()}
+AE_RULE_SLOTS = {"adagrad": 1, "sga": 1, "adadelta": 2, "adam": 2}
+AE_RULE_EPS = {"adagrad": 1e-6, "sga": 0.0, "adadelta": 1e-6, "adam": 1e-8}   # set_optimizer's default eps
+ACT ={"tanh": 0, "sigmoid": 1, "relu": 2}
 
 
 class VaebConfig(ctypes.Structure):
@@ -76,6 +82,12 @@ class AEConfigC(ctypes.Structure):
         ("max_batch", ctypes.c_int32), ("device", ctypes.c_int32), ("latent", ctypes.c_int32),
         ("iw_samples", ctypes.c_int32), ("corruption", ctypes.c_int32), ("prior", ctypes.c_int32),
     ]
+
+
+class AEOptimizerC(ctypes.Structure):
+    """vaeb_ae_optimizer (20 bytes)."""
+    _fields_ = [("rule", ctypes.c_int32), ("eta", ctypes.c_float), ("beta1", ctypes.c_float),
+                ("beta2", ctypes.c_float), ("eps", ctypes.c_float)]
 
 
 class VaebError(RuntimeError):
@@ -194,6 +206,12 @@ def load():
         "vaeb_ae_get_prior": ([_P, _F, _F], ctypes.c_int),
         "vaeb_ae_encode_bits": ([_P, _F, _I64, ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
         "vaeb_ae_decode_bits": ([_P, ctypes.POINTER(ctypes.c_uint32), _I64, _F], ctypes.c_int),
+        "vaeb_ae_set_optimizer": ([_P, ctypes.POINTER(AEOptimizerC)], ctypes.c_int),
+        "vaeb_ae_get_optimizer": ([_P, ctypes.POINTER(AEOptimizerC)], ctypes.c_int),
+        "vaeb_ae_set_opt_state": ([_P, ctypes.c_int32, _F, _I64], ctypes.c_int),
+        "vaeb_ae_get_opt_state": ([_P, ctypes.c_int32, _F, _I64], ctypes.c_int),
+        "vaeb_ae_set_opt_step": ([_P, _I64], ctypes.c_int),
+        "vaeb_ae_get_opt_step": ([_P, ctypes.POINTER(_I64)], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name, None)
@@ -588,7 +606,9 @@ class AEContext:
     scored on the clean rows; the evaluation calls never corrupt.
     prior="twomode" (latent="gauss" only; enum vaeb_ae_prior): per latent dimension the prior
     1/2 N(0, s^2) + 1/2 N(a, s^2) at set_prior's (mean1 a, width s), and the binary codes
-    encode_bits / decode_bits."""
+    encode_bits / decode_bits.
+    set_optimizer(rule, ...) (enum vaeb_ae_rule): gradient ascent with momentum, AdaDelta or Adam in
+    place of the AdaGrad(eta) a context starts with; get_opt_state / set_opt_state are its state slots."""
 
     def __init__(self, Dobs, Denc, Dz, Ddec, otype="binary", act="tanh", s2=1.0, eta=0.01, max_batch=100,
                  device=0, latent="point", iw_samples=1, corruption="none", prior="normal"):
@@ -662,6 +682,44 @@ class AEContext:
         out = np.empty(self.P, np.float32)
         check(self.lib.vaeb_ae_get_adagrad_state(self.h, fptr(out), out.size))
         return out
+
+    # ---- the update rule (vaeb_ae_set_optimizer; a fresh context: adagrad at the constructor's eta)
+    def set_optimizer(self, rule, eta, beta1=0.0, beta2=0.0, eps=None):
+        """rule: "adagrad" | "sga" | "adadelta" | "adam"; beta1 is the momentum (sga), rho (adadelta)
+        or beta1 (adam), beta2 adam's; eps None: the rule's default (adagrad's fixed 1e-6, sga 0,
+        adadelta 1e-6, adam 1e-8).  Another rule than the current one zeroes the optimiser state and
+        step; the same rule changes the numbers only (a step-size schedule)."""
+        if rule not in AE_RULE:
+            raise VaebError(f"rule {rule!r} not supported (adagrad | sga | adadelta | adam)")
+        o = AEOptimizerC(AE_RULE[rule], float(eta), float(beta1), float(beta2),
+                         float(AE_RULE_EPS[rule] if eps is None else eps))
+        check(self.lib.vaeb_ae_set_optimizer(self.h, ctypes.byref(o)))
+
+    def get_optimizer(self):
+        """(rule, eta, beta1, beta2, eps)."""
+        o = AEOptimizerC()
+        check(self.lib.vaeb_ae_get_optimizer(self.h, ctypes.byref(o)))
+        return AE_RULE_NAME[o.rule], o.eta, o.beta1, o.beta2, o.eps
+
+    def set_opt_state(self, slot, flat):
+        flat = np.ascontiguousarray(flat, np.float32)
+        check(self.lib.vaeb_ae_set_opt_state(self.h, int(slot), fptr(flat), flat.size))
+
+    def get_opt_state(self, slot):
+        """Slot 0 (adagrad's accumulator, sga's velocity, adadelta's g_ac, adam's m) or slot 1
+        (adadelta's dx_ac, adam's v), flat in theta order."""
+        out = np.empty(self.P, np.float32)
+        check(self.lib.vaeb_ae_get_opt_state(self.h, int(slot), fptr(out), out.size))
+        return out
+
+    def set_opt_step(self, t):
+        check(self.lib.vaeb_ae_set_opt_step(self.h, int(t)))
+
+    def get_opt_step(self):
+        """Optimiser steps taken since the rule was set (adam's t of the last step)."""
+        n = _I64()
+        check(self.lib.vaeb_ae_get_opt_step(self.h, ctypes.byref(n)))
+        return n.value
 
     def train(self, idx):
         idx = np.ascontiguousarray(idx, np.int32)

@@ -31,13 +31,21 @@ the prior 1/2 N(0, width^2) + 1/2 N(mean1, width^2) (include/vaeb_hip.h enum vae
 pulls the posterior means towards {0, mean1}; train.code(X) truncates them to Dz bits per row and
 train.decode_code(bits) decodes such codes.  train.set_prior(width=...) between epochs runs a schedule
 of falling widths.
+
+Update rules (the reference's other optimisers, infalg.py:44-137, and Adam): each constructor's `inf`
+may be infalg.AdaGrad (the default, AdaGrad(0.01), with theta_0, the context and the steps as ever),
+GradientAscent(eta, momentum), AdaDelta(rho, epsilon, eta) or Adam(eta, beta1, beta2, epsilon); the rule
+runs in the weight-gradient kernels' epilogue (include/vaeb_hip.h enum vaeb_ae_rule).  Every train has
+train.optimizer (the rule and its numbers as the engine holds them), train.set_eta(eta) (a step-size
+schedule between calls; the optimiser state is kept) and, under GradientAscent(eta, momentum=0),
+train.last_gradient() (the last step's gradient, one array per parameter).
 """
 from __future__ import annotations
 
 import numpy as np
 
 from . import _lib
-from .infalg import AdaGrad, bind_updates
+from .infalg import AdaGrad, BoundRule, bind_rule
 
 _ACT_NAMES = {"tanh": "tanh", "sigmoid": "sigmoid", "logistic": "sigmoid", "relu": "relu"}
 
@@ -97,8 +105,8 @@ class SharedParam:
 
 
 class _AccArena:
-    """Owner of the AdaGrad accumulators `inf.construct` hands out (views of the engine's
-    accumulator arena, one slice per SharedParam)."""
+    """Owner of the optimiser state `inf.construct` hands out: views of the engine's state arenas,
+    one slice per SharedParam -- slot 0 (the AdaGrad accumulators; v; g_ac; m) and slot 1 (dx_ac; v)."""
 
     def __init__(self, ctx):
         self.ctx = ctx
@@ -110,6 +118,14 @@ class _AccArena:
         flat = self.ctx.get_adagrad_state()
         flat[p.offset:p.offset + p.size] = value.ravel()
         self.ctx.set_adagrad_state(flat)
+
+    def _state_get(self, slot, p):
+        return self.ctx.get_opt_state(slot)[p.offset:p.offset + p.size].reshape(p.shape).copy()
+
+    def _state_set(self, slot, p, value):
+        flat = self.ctx.get_opt_state(slot)
+        flat[p.offset:p.offset + p.size] = value.ravel()
+        self.ctx.set_opt_state(slot, flat)
 
 
 CORRUPTIONS = ("mask", "saltpepper", "gauss")
@@ -125,15 +141,39 @@ def _corruption(corruption):
     return kind, float(level)
 
 
-class _DenoisingTrain:
-    """train(idx) of a corrupting context: callable as the plain train function, with the noise
-    level of the steps to come (set_noise / noise) and the corrupted rows a step would read."""
+class _Train:
+    """train(idx): one step of the engine on the rows Xtr[idx], returning its value; with the
+    update rule of the steps to come (optimizer / set_eta) and the gradient read-out."""
 
-    def __init__(self, ctx):
-        self.ctx = ctx
+    def __init__(self, ctx, theta):
+        self.ctx, self._theta = ctx, theta
 
     def __call__(self, idx):
         return self.ctx.train(np.asarray(idx, np.int32))
+
+    @property
+    def optimizer(self):
+        """BoundRule(rule, eta, beta1, beta2, eps) as the engine holds it."""
+        return BoundRule(*self.ctx.get_optimizer())
+
+    def set_eta(self, eta):
+        """The step size of the steps to come, state and step counter kept: a schedule."""
+        rule, _, b1, b2, eps = self.ctx.get_optimizer()
+        self.ctx.set_optimizer(rule, eta, b1, b2, eps)
+
+    def last_gradient(self):
+        """The last step's gradient of the objective (the prior on theta included), one array per
+        parameter: what GradientAscent(momentum=0) leaves in state slot 0."""
+        o = self.optimizer
+        if o.rule != "sga" or o.beta1 != 0:
+            raise ValueError("last_gradient() needs inf=GradientAscent(eta, momentum=0): only that rule stores the gradient")
+        flat = self.ctx.get_opt_state(0)
+        return [flat[p.offset:p.offset + p.size].reshape(p.shape).copy() for p in self._theta]
+
+
+class _DenoisingTrain(_Train):
+    """train(idx) of a corrupting context: with the noise level of the steps to come (set_noise /
+    noise) and the corrupted rows a step would read."""
 
     def set_noise(self, level):
         self.ctx.set_corruption_level(level)
@@ -222,21 +262,19 @@ def _construct(latent, Xtr, Denc, Dz, Ddec, f, s2, inf, otype, max_batch, device
     ctx.set_params(np.concatenate([t.ravel() for t in theta0]))
     offs = np.cumsum([0] + [int(np.prod(s)) for _, s in shapes])
     theta = [SharedParam(ctx, n, s, int(o)) for (n, s), o in zip(shapes, offs[:-1])]
-    # ae.py:80: updates = inf.construct(logjoint, theta), bound to the engine's fused rule
+    # ae.py:80: updates = inf.construct(logjoint, theta), bound to the engine's fused rule.  AdaGrad
+    # is the context's own from vaeb_ae_create (eta above); any other rule is set once
     arena = _AccArena(ctx)
     updates = inf.construct(arena, theta)
-    bind_updates(arena, theta, updates)
+    bound = bind_rule(arena, theta, updates)
+    if bound.rule != "adagrad":
+        ctx.set_optimizer(*bound)
 
     if kind != "none":
         ctx.set_corruption_noise(_lib.EPS_PHILOX, corruption_seed)
         ctx.set_corruption_level(level)
-        return _DenoisingTrain(ctx), ctx, theta
-
-    def train(idx):
-        return ctx.train(np.asarray(idx, np.int32))
-
-    train.ctx = ctx
-    return train, ctx, theta
+        return _DenoisingTrain(ctx, theta), ctx, theta
+    return _Train(ctx, theta), ctx, theta
 
 
 def ConstructAE(Xtr, Denc=(500,), Dz=20, Ddec=(500,), f="tanh", s2=1.0, inf=None, otype="binary",

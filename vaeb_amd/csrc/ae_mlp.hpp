@@ -38,6 +38,7 @@
 //                                                           PAeBwdT<true, true> (mode LATENT_IW)
 //   weight gradients:     [in | 1]^T dout (ones row = bias gradient), prior -theta/s2 and
 //                         AdaGrad (infalg.py:155-161) in the epilogue   PAeWgrad
+//                         (or gradient ascent with momentum, AdaDelta, Adam: PAeWgradT<RULE>)
 // The first layer's A operand is gathered on the fly through idx (no copy of Xtr[idx]).
 // Every weight is updated only after the last kernel of the step that reads it, so the
 // update is simultaneous in the Theano sense.
@@ -332,10 +333,31 @@ struct PAeBwdT : AeBwdIwArgs<IW>, AePriorArgs<TM> {
 };
 using PAeBwd = PAeBwdT<false>;
 
-// ---------------------------------------------------------------- weight gradient + AdaGrad
+// ---------------------------------------------------------------- weight gradient + update rule
 // C[Kin + 1 x N] = [in | 1]^T dout over the M batch rows (row Kin = the bias gradient),
-// g = C - theta / s2 (mlp.py:87-91 prior), acc += g^2, theta += eta g / (sqrt(acc) + 1e-6).
-struct PAeWgrad {
+// g = C - theta / s2 (mlp.py:87-91 prior), then the context's rule (include/vaeb_hip.h enum
+// vaeb_ae_rule), every rule ascending.  accum is slot 0 of the optimiser state, state1 slot 1,
+// both indexed as theta; element (m, n) of theta belongs to one lane, which reads and writes its
+// theta and state with plain loads and stores:
+//   RULE_ADAGRAD   (infalg.py:155-161)  acc += g^2, theta += eta g / (sqrt(acc) + 1e-6)
+//   RULE_SGA       (infalg.py:44-74 + momentum)  v' = mu v + g, theta += eta v'
+//                  (mu = 0: slot 0 holds g, stored as computed -- the engine's gradient read-out)
+//   RULE_ADADELTA  (infalg.py:88-106)   g_ac' = rho g_ac + (1 - rho) g^2,
+//                  dx = sqrt(dx_ac + eps) g / sqrt(g_ac' + eps), theta += eta dx,
+//                  dx_ac' = rho dx_ac + (1 - rho) dx^2          (slot 0 g_ac, slot 1 dx_ac)
+//   RULE_ADAM      m' = b1 m + (1 - b1) g, v' = b2 v + (1 - b2) g^2,
+//                  theta += eta (m' / bc1) / (sqrt(v' / bc2) + eps)   (slot 0 m, slot 1 v;
+//                  bc_i = 1 - b_i^t by value: the host forms them per step in double)
+// A rule's extra arguments and its branch exist only in its own instantiation (an empty base for
+// AdaGrad), so PAeWgrad's kernel and kernel arguments are what they were without the others.
+enum : int { RULE_ADAGRAD = 0, RULE_SGA = 1, RULE_ADADELTA = 2, RULE_ADAM = 3 };
+template <int RULE> struct AeRuleArgs {};
+template <> struct AeRuleArgs<RULE_SGA> { float mu; };
+template <> struct AeRuleArgs<RULE_ADADELTA> { float* state1; float rho, eps; };
+template <> struct AeRuleArgs<RULE_ADAM> { float* state1; float b1, b2, eps, bc1, bc2; };
+
+template <int RULE>
+struct PAeWgradT : AeRuleArgs<RULE> {
     Dbg a;
     int M, N, K;                     // M = Kin + 1, N = out width, K = batch rows
     const float* in; int ldin; int in_rows; const int* idx; int Kin;
@@ -376,12 +398,32 @@ struct PAeWgrad {
             const int64_t i = (m == Kin) ? offb + n : offW + (int64_t)m * N + n;
             const float th = theta[i];
             const float g = acc[0][r] - th * inv_s2;
-            const float ac = accum[i] + g * g;
-            accum[i] = ac;
-            theta[i] = th + eta * g / (sqrtf(ac) + 1e-6f);
+            if constexpr (RULE == RULE_SGA) {
+                const float v = this->mu * accum[i] + g;
+                accum[i] = v;
+                theta[i] = th + eta * v;
+            } else if constexpr (RULE == RULE_ADADELTA) {
+                const float dxa = this->state1[i];
+                const float ga = this->rho * accum[i] + (1.f - this->rho) * (g * g);
+                const float dx = sqrtf(dxa + this->eps) * g / sqrtf(ga + this->eps);
+                accum[i] = ga;
+                this->state1[i] = this->rho * dxa + (1.f - this->rho) * (dx * dx);
+                theta[i] = th + eta * dx;
+            } else if constexpr (RULE == RULE_ADAM) {
+                const float m1 = this->b1 * accum[i] + (1.f - this->b1) * g;
+                const float v1 = this->b2 * this->state1[i] + (1.f - this->b2) * (g * g);
+                accum[i] = m1;
+                this->state1[i] = v1;
+                theta[i] = th + eta * (m1 / this->bc1) / (sqrtf(v1 / this->bc2) + this->eps);
+            } else {
+                const float ac = accum[i] + g * g;
+                accum[i] = ac;
+                theta[i] = th + eta * g / (sqrtf(ac) + 1e-6f);
+            }
         }
     }
 };
+using PAeWgrad = PAeWgradT<RULE_ADAGRAD>;
 
 // Log-likelihood of the step: fixed-order fp64 sum of the [M][nct] partials -> out[slot]
 // (= loglik / M, the value train() returns, ae.py:86).

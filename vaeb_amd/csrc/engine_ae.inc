@@ -18,6 +18,9 @@
 //                         ae_decode_hidden | ae_output(VALUE) | iw_lse_kernel, then ae_sum_to_host
 //   vaeb_ae_encode_bits   ae_chunks: ae_encode (zero noise) | ae_pack_bits_kernel
 //   vaeb_ae_decode_bits   ae_chunks: ae_unpack_bits_kernel | ae_decode_hidden | ae_output(PREDICT)
+//   vaeb_ae_set_optimizer the rule and hyper-parameters ae_wgrad launches with (PAeWgradT<RULE>, a host
+//                         switch there and nowhere else); another rule: both state slots and the
+//                         optimiser step counter zeroed on the stream
 // A context of the two-mode latent prior (c.prior, ae_two_mode) runs the same sequences with the TM
 // instantiations of the latent forward, the decoder's first-layer backward and the sample kernel;
 // every other context launches what it launched before.
@@ -79,6 +82,12 @@ struct vaeb_ae {
     // arguments as the level above; a chunk's code words [max_batch x ceil(Dz / 32)] (first use)
     float pr_mean1 = 1.f, pr_width = 0.25f;
     uint32_t* code_w = nullptr;
+    // the update rule (vaeb_ae_set_optimizer; {ADAGRAD, c.eta, 0, 0, 1e-6} from create): launch
+    // arguments as the prior above.  acc is slot 0 of its state, acc2 slot 1 (allocated when a
+    // two-slot rule is first set); opt_t counts the optimiser steps taken (Adam's t - 1 of the next)
+    vaeb_ae_optimizer opt{};
+    float* acc2 = nullptr;
+    int64_t opt_t = 0;
 };
 
 namespace {
@@ -243,16 +252,42 @@ int ae_output(vaeb_ae* a, int M, AeOut what, const AeRows& y = AeRows{}) {
 }
 
 // ------------------------------------------------------------------ backward
-// One weight-gradient + AdaGrad launch for layer l from its input in (gathered through
-// in.idx for the first layer) and its output delta over M rows.
+// A rule's own launch arguments into its parameter block (nothing into AdaGrad's: the overload is
+// chosen by the block's base).  Adam's bias corrections are those of the step being enqueued,
+// t = opt_t + 1, formed in double: every step of a vaeb_ae_train_many carries its own.
+bool ae_two_slot(int rule) { return rule == VAEB_AE_RULE_ADADELTA || rule == VAEB_AE_RULE_ADAM; }
+void ae_put_rule(const vaeb_ae*, ae::AeRuleArgs<ae::RULE_ADAGRAD>&) {}
+void ae_put_rule(const vaeb_ae* a, ae::AeRuleArgs<ae::RULE_SGA>& q) { q.mu = a->opt.beta1; }
+void ae_put_rule(const vaeb_ae* a, ae::AeRuleArgs<ae::RULE_ADADELTA>& q) {
+    q.state1 = a->acc2; q.rho = a->opt.beta1; q.eps = a->opt.eps;
+}
+void ae_put_rule(const vaeb_ae* a, ae::AeRuleArgs<ae::RULE_ADAM>& q) {
+    const double t = (double)(a->opt_t + 1);
+    q.state1 = a->acc2; q.b1 = a->opt.beta1; q.b2 = a->opt.beta2; q.eps = a->opt.eps;
+    q.bc1 = (float)(1.0 - std::pow((double)a->opt.beta1, t));
+    q.bc2 = (float)(1.0 - std::pow((double)a->opt.beta2, t));
+}
+
+// One weight-gradient + update launch for layer l from its input in (gathered through in.idx for
+// the first layer) and its output delta over M rows, in the instantiation of the context's rule:
+// the one place that launches the update.
 int ae_wgrad(vaeb_ae* a, const AeLayer& l, const AeRows& in, const float* dout, int M) {
-    ae::PAeWgrad p{};
-    p.M = l.K + 1; p.N = l.N; p.K = M;
-    p.in = in.p; p.ldin = l.K; p.in_rows = in.rows; p.idx = in.idx; p.Kin = l.K;
-    p.dout = dout;
-    p.theta = a->theta; p.accum = a->acc; p.offW = l.oW; p.offb = l.ob;
-    p.eta = a->c.eta; p.inv_s2 = 1.0f / a->c.s2;
-    launch_bigk<1>(a->s, p);
+    auto launch = [&](auto p) {
+        p.M = l.K + 1; p.N = l.N; p.K = M;
+        p.in = in.p; p.ldin = l.K; p.in_rows = in.rows; p.idx = in.idx; p.Kin = l.K;
+        p.dout = dout;
+        p.theta = a->theta; p.accum = a->acc; p.offW = l.oW; p.offb = l.ob;
+        p.eta = a->opt.eta; p.inv_s2 = 1.0f / a->c.s2;
+        ae_put_rule(a, p);
+        launch_bigk<1>(a->s, p);
+    };
+    switch (a->opt.rule) {
+    case VAEB_AE_RULE_ADAGRAD: launch(ae::PAeWgrad{}); break;
+    case VAEB_AE_RULE_SGA: launch(ae::PAeWgradT<ae::RULE_SGA>{}); break;
+    case VAEB_AE_RULE_ADADELTA: launch(ae::PAeWgradT<ae::RULE_ADADELTA>{}); break;
+    case VAEB_AE_RULE_ADAM: launch(ae::PAeWgradT<ae::RULE_ADAM>{}); break;
+    default: return fail(VAEB_ERR_STATE, "unknown update rule %d", a->opt.rule);
+    }
     CHECK_LAUNCH();
     return 0;
 }
@@ -396,6 +431,7 @@ int ae_step(vaeb_ae* a, const int* idx, int M, int slot, int64_t lb, int64_t n) 
     }
     if (int rc = ae_bwd_encoder(a, xe, M)) return rc;
     if (gauss || ae_corrupting(a)) ++a->step;
+    ++a->opt_t;   // one optimiser step, whatever the rule (not the Philox counter above)
     return 0;
 }
 
@@ -507,6 +543,7 @@ int vaeb_ae_create(const vaeb_ae_config* cfg, vaeb_ae** out) {
         return fail(VAEB_ERR_ARG, "corruption needs max_batch * Dobs < 2^29 (the corrupted rows' 32-bit byte offsets)");
     auto* a = new vaeb_ae();
     a->c = g;
+    a->opt = vaeb_ae_optimizer{VAEB_AE_RULE_ADAGRAD, g.eta, 0.f, 0.f, 1e-6f};
     if (hipSetDevice(g.device) != hipSuccess || hipStreamCreateWithFlags(&a->s, hipStreamNonBlocking) != hipSuccess) {
         delete a;
         return fail(VAEB_ERR_HIP, "device / stream init failed");
@@ -596,6 +633,87 @@ int vaeb_ae_set_params(vaeb_ae* a, const float* f, int64_t n) { return ae_xfer(a
 int vaeb_ae_get_params(vaeb_ae* a, float* f, int64_t n) { return ae_xfer(a, a ? a->theta : nullptr, nullptr, f, n); }
 int vaeb_ae_set_adagrad_state(vaeb_ae* a, const float* f, int64_t n) { return ae_xfer(a, a ? a->acc : nullptr, f, nullptr, n); }
 int vaeb_ae_get_adagrad_state(vaeb_ae* a, float* f, int64_t n) { return ae_xfer(a, a ? a->acc : nullptr, nullptr, f, n); }
+
+// ------------------------------------------------------------------ the update rule
+// The fields a rule does not use are 0 (AdaGrad's eps: the kernel's literal 1e-6).
+int vaeb_ae_set_optimizer(vaeb_ae* a, const vaeb_ae_optimizer* o) {
+    if (!a || !o) return fail(VAEB_ERR_ARG, "null argument");
+    auto unit = [](float b) { return b >= 0.f && b < 1.f; };   // NaN fails
+    const char* why = nullptr;
+    if (!(o->eta > 0.f) || !std::isfinite(o->eta)) why = "eta must be finite and > 0";
+    else switch (o->rule) {
+    case VAEB_AE_RULE_ADAGRAD:
+        if (o->eps != 1e-6f) why = "AdaGrad's eps is 1e-6 (the kernel's literal)";
+        else if (o->beta1 != 0.f || o->beta2 != 0.f) why = "AdaGrad uses no beta: beta1 and beta2 must be 0";
+        break;
+    case VAEB_AE_RULE_SGA:
+        if (!unit(o->beta1)) why = "the momentum (beta1) must be in [0, 1)";
+        else if (o->beta2 != 0.f || o->eps != 0.f) why = "gradient ascent uses beta1 alone: beta2 and eps must be 0";
+        break;
+    case VAEB_AE_RULE_ADADELTA:
+        if (!unit(o->beta1) || o->beta1 == 0.f) why = "rho (beta1) must be in (0, 1)";
+        else if (!(o->eps > 0.f) || !std::isfinite(o->eps)) why = "eps must be finite and > 0";
+        else if (o->beta2 != 0.f) why = "AdaDelta uses no beta2: it must be 0";
+        break;
+    case VAEB_AE_RULE_ADAM:
+        if (!unit(o->beta1) || !unit(o->beta2)) why = "beta1 and beta2 must be in [0, 1)";
+        else if (!(o->eps > 0.f) || !std::isfinite(o->eps)) why = "eps must be finite and > 0";
+        break;
+    default: why = "rule must be VAEB_AE_RULE_ADAGRAD | _SGA | _ADADELTA | _ADAM";
+    }
+    if (why)
+        return fail(VAEB_ERR_ARG, "optimizer {rule %d, eta %g, beta1 %g, beta2 %g, eps %g}: %s", o->rule, (double)o->eta,
+                    (double)o->beta1, (double)o->beta2, (double)o->eps, why);
+    if (o->rule != a->opt.rule) {   // another rule: its state starts from zero, after the enqueued steps
+        if (ae_two_slot(o->rule))
+            if (int rc = a->mem.lazy(&a->acc2, a->P)) return rc;
+        HIP_TRY(hipMemsetAsync(a->acc, 0, sizeof(float) * (size_t)a->P, a->s));
+        if (a->acc2) HIP_TRY(hipMemsetAsync(a->acc2, 0, sizeof(float) * (size_t)a->P, a->s));
+        a->opt_t = 0;
+    }
+    a->opt = *o;   // launch arguments: the enqueued steps keep theirs
+    return 0;
+}
+
+int vaeb_ae_get_optimizer(vaeb_ae* a, vaeb_ae_optimizer* o) {
+    if (!a || !o) return fail(VAEB_ERR_ARG, "null argument");
+    *o = a->opt;
+    return 0;
+}
+
+static float* ae_opt_slot(vaeb_ae* a, int32_t slot) {
+    if (!a) return nullptr;
+    if (slot == 0) return a->acc;
+    if (slot == 1 && ae_two_slot(a->opt.rule)) return a->acc2;
+    fail(VAEB_ERR_ARG, "optimizer state slot %d: rule %d has slot 0%s", slot, a->opt.rule,
+         ae_two_slot(a->opt.rule) ? " and slot 1" : " only");
+    return nullptr;
+}
+
+int vaeb_ae_set_opt_state(vaeb_ae* a, int32_t slot, const float* f, int64_t n) {
+    if (!a || !f) return fail(VAEB_ERR_ARG, "null argument");
+    float* dev = ae_opt_slot(a, slot);
+    return dev ? ae_xfer(a, dev, f, nullptr, n) : VAEB_ERR_ARG;
+}
+
+int vaeb_ae_get_opt_state(vaeb_ae* a, int32_t slot, float* f, int64_t n) {
+    if (!a || !f) return fail(VAEB_ERR_ARG, "null argument");
+    float* dev = ae_opt_slot(a, slot);
+    return dev ? ae_xfer(a, dev, nullptr, f, n) : VAEB_ERR_ARG;
+}
+
+int vaeb_ae_set_opt_step(vaeb_ae* a, int64_t t) {
+    if (!a) return fail(VAEB_ERR_ARG, "null argument");
+    if (t < 0) return fail(VAEB_ERR_ARG, "optimizer step %lld < 0", (long long)t);
+    a->opt_t = t;
+    return 0;
+}
+
+int vaeb_ae_get_opt_step(vaeb_ae* a, int64_t* t) {
+    if (!a || !t) return fail(VAEB_ERR_ARG, "null argument");
+    *t = a->opt_t;
+    return 0;
+}
 
 int vaeb_ae_train_many(vaeb_ae* a, const int32_t* idx, int32_t n, int32_t batch, float* out) {
     if (!a || !idx || !out || n <= 0 || batch <= 0) return fail(VAEB_ERR_ARG, "bad arguments");
