@@ -505,6 +505,102 @@ int vaeb_ae_get_opt_state(vaeb_ae* ae, int32_t slot, float* flat, int64_t n);
 int vaeb_ae_set_opt_step(vaeb_ae* ae, int64_t t);
 int vaeb_ae_get_opt_step(vaeb_ae* ae, int64_t* t);
 
+/* ------------------------------------------------------------------------------------------
+ * Softmax MLP classifier on the layer stack (the reference's degenerate-vae/mlp.py:104-153 the MAP
+ * classifier, :263-329 the dropout one, :332-388 its learning loop): hidden layers
+ * H_{i+1} = f(H_i W_i + b_i), H_0 = X, logits a = H_n Wout + bout, P = softmax(a) (logpdf.py:16-17).
+ * Targets Y are a float matrix [n x Dout] in [0, 1] (1-hot in the reference), not class indices.
+ * Per row, with e = exp(a - max a) and P = e / sum e:
+ *   VAEB_CLF_BERNOULLI    ll = sum_j Y_j log(P_j + 1e-7) + (1 - Y_j) log(1 - P_j + 1e-7)   (mlp.py:112),
+ *                         dll/da_i = P_i (dP_i - sum_j P_j dP_j),
+ *                         dP_j = Y_j / (P_j + 1e-7) - (1 - Y_j) / (1 - P_j + 1e-7)
+ *   VAEB_CLF_CATEGORICAL  (extension) ll = sum_j Y_j (a_j - max a - log sum e),  dll/da_i = Y_i - P_i sum_j Y_j
+ * The objective f of a step on M rows is the SUM of the rows' ll, plus with prior = 1 the N(0, s2)
+ * prior on theta (gradient - theta / s2); prior = 0 is the reference ("logjoint = loglik #+ logprior").
+ * Every update rule of vaeb_ae_optimizer ascends f; a fresh context is {ADAGRAD, cfg.eta, 0, 0, 1e-6}.
+ * Theta is flat float32 in the reference's order (mlp.py:113, 277): W0..W{n-1}, b0..b{n-1}, Wout,
+ * bout; W row-major [in x out].
+ *
+ * Weight dropout (dropout = 1; mlp.py:265-277 at keep = 0.5): every call of the network uses
+ * theta~ = theta * m with a fresh m ~ Bernoulli(keep) per PARAMETER (weights and biases alike).  A
+ * training step draws m, runs the forward and the data backward on theta~, and applies the rule to
+ * the real theta with g = m * (the weight gradient) - theta / s2: a dropped parameter sees the
+ * prior's pull alone (0 without a prior), and the rule does with that whatever it does.
+ * The draw: parameter i of the flat arena takes output word i & 3 of the Philox4x32-10 block at
+ *   c0 = i >> 2,  c1 = 0x40000000 (a site of its own: the latent draws have c1 < 2^30, the input
+ *   corruption sets bit 31),  c2, c3 = the step word of "Noise" above: domain 0 at the context's
+ *   step counter for training, domain 1 | (l + 1) << 1 for evaluation draw l,
+ * under the key (seed lo, seed hi), and is kept iff word < T, T = floor(keep * 2^32) computed once
+ * in double from the float32 keep (so the kept fraction is T / 2^32 <= keep, below it by less than
+ * 2^-32; keep = 1 gives T = 2^32 and keeps every parameter: such a context steps bit for bit as
+ * a dropout = 0 context).  The step counter advances by one per training step on EVERY context, so
+ * a schedule means the same on a MAP and a dropout context; evaluation calls leave it.
+ *
+ * Every bad argument is VAEB_ERR_ARG before the device is touched, with the state unchanged: at
+ * create Din <= 0, n_hidden outside 1..VAEB_AE_MAX_LAYERS, a Dh <= 0, Dout < 2, an unknown act /
+ * loss / prior / dropout, prior = 1 without a finite s2 > 0, eta not finite and > 0, max_batch <= 0,
+ * dropout = 1 with keep outside (0, 1] or not finite. */
+enum vaeb_clf_loss { VAEB_CLF_BERNOULLI = 0, VAEB_CLF_CATEGORICAL = 1 };
+typedef struct vaeb_clf_config {
+    int32_t Din;                          /* input size                                       */
+    int32_t n_hidden;                     /* len(Dh), 1..VAEB_AE_MAX_LAYERS                   */
+    int32_t Dh[VAEB_AE_MAX_LAYERS];       /* hidden sizes                                     */
+    int32_t Dout;                         /* classes, >= 2 (offset 40)                        */
+    int32_t act;                          /* enum vaeb_act                                    */
+    int32_t loss;                         /* enum vaeb_clf_loss                               */
+    int32_t prior;                        /* 0: none (the reference); 1: N(0, s2) on theta    */
+    float   s2;                           /* prior variance (read with prior = 1)             */
+    float   eta;                          /* AdaGrad step size of the rule in force at create */
+    int32_t max_batch;                    /* largest training batch / evaluation chunk        */
+    int32_t device;
+    int32_t dropout;                      /* 0: MAP classifier; 1: weight dropout (offset 72) */
+    float   keep;                         /* Bernoulli keep probability (read with dropout = 1) */
+} vaeb_clf_config;                        /* 80 bytes                                         */
+
+typedef struct vaeb_clf vaeb_clf;
+
+int vaeb_clf_create(const vaeb_clf_config* cfg, vaeb_clf** out);
+int vaeb_clf_destroy(vaeb_clf* clf);
+int vaeb_clf_num_params(const vaeb_clf* clf, int64_t* n);
+/* Xtr [n_rows x Din] and Ytr [n_rows x Dout], both copied to the device. */
+int vaeb_clf_set_data(vaeb_clf* clf, const float* x, const float* y, int64_t n_rows);
+int vaeb_clf_set_params(vaeb_clf* clf, const float* flat, int64_t n);
+int vaeb_clf_get_params(vaeb_clf* clf, float* flat, int64_t n);
+/* The update rule and its state: the semantics and argument checks of the vaeb_ae_* calls of the
+ * same names (slot 0 is AdaGrad's accumulator; under SGA at momentum 0 it holds the last step's
+ * gradient g). */
+int vaeb_clf_set_optimizer(vaeb_clf* clf, const vaeb_ae_optimizer* opt);
+int vaeb_clf_get_optimizer(vaeb_clf* clf, vaeb_ae_optimizer* out);
+int vaeb_clf_set_opt_state(vaeb_clf* clf, int32_t slot, const float* flat, int64_t n);
+int vaeb_clf_get_opt_state(vaeb_clf* clf, int32_t slot, float* flat, int64_t n);
+int vaeb_clf_set_opt_step(vaeb_clf* clf, int64_t t);
+int vaeb_clf_get_opt_step(vaeb_clf* clf, int64_t* t);
+/* The dropout draws' Philox key and step counter (seed 0, step 0 after create); accepted on any
+ * context. */
+int vaeb_clf_set_seed(vaeb_clf* clf, uint64_t seed);
+int vaeb_clf_set_step(vaeb_clf* clf, int64_t step);
+int vaeb_clf_get_step(vaeb_clf* clf, int64_t* step);
+/* One step on the rows idx [n] of the resident data (n <= max_batch, every index in range, else
+ * VAEB_ERR_ARG); writes the step's log-likelihood SUM (the reference's outputs=logjoint): the
+ * fixed-order fp64 sum of the row values, stored as float.  train_many: consecutive batch-sized
+ * slices of idx, the last partial slice kept, out[j] the value of slice j, one host sync. */
+int vaeb_clf_train(vaeb_clf* clf, const int32_t* idx, int32_t n, float* out_loglik_sum);
+int vaeb_clf_train_many(vaeb_clf* clf, const int32_t* idx, int32_t n, int32_t batch, float* out);
+/* The evaluation calls take host rows, run in max_batch chunks (n need not fit max_batch) and
+ * change no parameter, optimiser state or step.  `draws` = 0 (`draw` = -1) uses theta as it is;
+ * draws = L >= 1 (L <= 2^20) is valid on dropout contexts only and averages softmax under theta~
+ * over the evaluation draws 0..L-1, accumulated on the device; draw >= 0 uses that one evaluation
+ * draw.  Equal calls return equal bits.
+ * predict: P [n x Dout].  loglik: the fp64 sum over the rows of ll (no prior).  accuracy: the
+ * number of rows with y[i][argmax_j P_ij] == 1 (mlp.py:367-373; the lowest index among equal P, as
+ * numpy.argmax), counted on the device in integers. */
+int vaeb_clf_predict(vaeb_clf* clf, const float* x, int64_t n, int32_t draws, float* out);
+int vaeb_clf_loglik(vaeb_clf* clf, const float* x, const float* y, int64_t n, int32_t draw, double* out_sum);
+int vaeb_clf_accuracy(vaeb_clf* clf, const float* x, const float* y, int64_t n, int32_t draws, int64_t* correct);
+/* The byte mask m [num_params] (1 kept, 0 dropped) of the training step at `step` (draw = -1) or of
+ * evaluation draw `draw` >= 0 at `step`; dropout contexts only.  Changes no state. */
+int vaeb_clf_draw_mask(vaeb_clf* clf, int64_t step, int32_t draw, uint8_t* out);
+
 #ifdef __cplusplus
 }
 #endif

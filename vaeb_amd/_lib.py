@@ -44,6 +44,11 @@ EXPORTS = [
     "vaeb_ae_set_prior", "vaeb_ae_get_prior", "vaeb_ae_encode_bits", "vaeb_ae_decode_bits",
     "vaeb_ae_set_optimizer", "vaeb_ae_get_optimizer", "vaeb_ae_set_opt_state", "vaeb_ae_get_opt_state",
     "vaeb_ae_set_opt_step", "vaeb_ae_get_opt_step",
+    "vaeb_clf_create", "vaeb_clf_destroy", "vaeb_clf_num_params", "vaeb_clf_set_data", "vaeb_clf_set_params",
+    "vaeb_clf_get_params", "vaeb_clf_set_optimizer", "vaeb_clf_get_optimizer", "vaeb_clf_set_opt_state",
+    "vaeb_clf_get_opt_state", "vaeb_clf_set_opt_step", "vaeb_clf_get_opt_step", "vaeb_clf_set_seed",
+    "vaeb_clf_set_step", "vaeb_clf_get_step", "vaeb_clf_train", "vaeb_clf_train_many", "vaeb_clf_predict",
+    "vaeb_clf_loglik", "vaeb_clf_accuracy", "vaeb_clf_draw_mask",
 ]
 DIAG_EXPORTS = ["vaeb_profile_steps", "vaeb_kernel_name", "vaeb_debug_timeline", "vaeb_test_gemm_bf16",
                 "vaeb_bench_gemm_bf16", "vaeb_graph_status", "vaeb_comm_info", "vaeb_time_update_many", "vaeb_busy",
@@ -61,6 +66,7 @@ AE_RULE_NAME = {v: k for k, v in AE_RULE.items()}
 AE_RULE_SLOTS = {"adagrad": 1, "sga": 1, "adadelta": 2, "adam": 2}
 AE_RULE_EPS = {"adagrad": 1e-6, "sga": 0.0, "adadelta": 1e-6, "adam": 1e-8}   # set_optimizer's default eps
 ACT ={"tanh": 0, "sigmoid": 1, "relu": 2}
+CLF_LOSS = {"bernoulli": 0, "categorical": 1}   # enum vaeb_clf_loss
 
 
 class VaebConfig(ctypes.Structure):
@@ -81,6 +87,16 @@ class AEConfigC(ctypes.Structure):
         ("otype", ctypes.c_int32), ("act", ctypes.c_int32), ("s2", ctypes.c_float), ("eta", ctypes.c_float),
         ("max_batch", ctypes.c_int32), ("device", ctypes.c_int32), ("latent", ctypes.c_int32),
         ("iw_samples", ctypes.c_int32), ("corruption", ctypes.c_int32), ("prior", ctypes.c_int32),
+    ]
+
+
+class CLFConfigC(ctypes.Structure):
+    """vaeb_clf_config (80 bytes)."""
+    _fields_ = [
+        ("Din", ctypes.c_int32), ("n_hidden", ctypes.c_int32), ("Dh", ctypes.c_int32 * 8), ("Dout", ctypes.c_int32),
+        ("act", ctypes.c_int32), ("loss", ctypes.c_int32), ("prior", ctypes.c_int32), ("s2", ctypes.c_float),
+        ("eta", ctypes.c_float), ("max_batch", ctypes.c_int32), ("device", ctypes.c_int32),
+        ("dropout", ctypes.c_int32), ("keep", ctypes.c_float),
     ]
 
 
@@ -212,6 +228,27 @@ def load():
         "vaeb_ae_get_opt_state": ([_P, ctypes.c_int32, _F, _I64], ctypes.c_int),
         "vaeb_ae_set_opt_step": ([_P, _I64], ctypes.c_int),
         "vaeb_ae_get_opt_step": ([_P, ctypes.POINTER(_I64)], ctypes.c_int),
+        "vaeb_clf_create": ([ctypes.POINTER(CLFConfigC), ctypes.POINTER(_P)], ctypes.c_int),
+        "vaeb_clf_destroy": ([_P], ctypes.c_int),
+        "vaeb_clf_num_params": ([_P, ctypes.POINTER(_I64)], ctypes.c_int),
+        "vaeb_clf_set_data": ([_P, _F, _F, _I64], ctypes.c_int),
+        "vaeb_clf_set_params": ([_P, _F, _I64], ctypes.c_int),
+        "vaeb_clf_get_params": ([_P, _F, _I64], ctypes.c_int),
+        "vaeb_clf_set_optimizer": ([_P, ctypes.POINTER(AEOptimizerC)], ctypes.c_int),
+        "vaeb_clf_get_optimizer": ([_P, ctypes.POINTER(AEOptimizerC)], ctypes.c_int),
+        "vaeb_clf_set_opt_state": ([_P, ctypes.c_int32, _F, _I64], ctypes.c_int),
+        "vaeb_clf_get_opt_state": ([_P, ctypes.c_int32, _F, _I64], ctypes.c_int),
+        "vaeb_clf_set_opt_step": ([_P, _I64], ctypes.c_int),
+        "vaeb_clf_get_opt_step": ([_P, ctypes.POINTER(_I64)], ctypes.c_int),
+        "vaeb_clf_set_seed": ([_P, ctypes.c_uint64], ctypes.c_int),
+        "vaeb_clf_set_step": ([_P, _I64], ctypes.c_int),
+        "vaeb_clf_get_step": ([_P, ctypes.POINTER(_I64)], ctypes.c_int),
+        "vaeb_clf_train": ([_P, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, _F], ctypes.c_int),
+        "vaeb_clf_train_many": ([_P, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32, _F], ctypes.c_int),
+        "vaeb_clf_predict": ([_P, _F, _I64, ctypes.c_int32, _F], ctypes.c_int),
+        "vaeb_clf_loglik": ([_P, _F, _F, _I64, ctypes.c_int32, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
+        "vaeb_clf_accuracy": ([_P, _F, _F, _I64, ctypes.c_int32, ctypes.POINTER(_I64)], ctypes.c_int),
+        "vaeb_clf_draw_mask": ([_P, _I64, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint8)], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name, None)
@@ -853,4 +890,154 @@ class AEContext:
         out = np.empty((words.shape[0], self.Dobs), np.float32)
         check(self.lib.vaeb_ae_decode_bits(self.h, words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), words.shape[0],
                                            fptr(out)))
+        return out
+
+
+class CLFContext:
+    """One softmax MLP classifier (vaeb_clf_*) on one GPU: tanh / sigmoid / relu hidden layers, a
+    softmax output scored by loss="bernoulli" (the reference's mlp.py:112) or "categorical",
+    prior=True for the N(0, s2) prior on theta (the reference leaves it out), dropout=True for weight
+    dropout at `keep` (a fresh Bernoulli(keep) mask per parameter and call, device Philox keyed by
+    set_seed and the step counter).  train / train_many return log-likelihood SUMS.  The optimiser
+    calls take and return the tuples of AEContext."""
+
+    def __init__(self, Din, Dh, Dout, act="tanh", loss="bernoulli", prior=False, s2=1.0, eta=0.01, max_batch=100,
+                 device=0, dropout=False, keep=0.5):
+        self.lib = load()
+        c = CLFConfigC()
+        Dh = list(Dh)
+        if not 1 <= len(Dh) <= AE_MAX_LAYERS:
+            raise VaebError(f"1..{AE_MAX_LAYERS} hidden layers are supported")
+        c.Din, c.n_hidden, c.Dout = int(Din), len(Dh), int(Dout)
+        for i, d in enumerate(Dh):
+            c.Dh[i] = int(d)
+        if loss not in CLF_LOSS:
+            raise VaebError(f"loss {loss!r} not supported (bernoulli | categorical)")
+        c.act, c.loss = ACT[act], CLF_LOSS[loss]
+        c.prior, c.s2, c.eta = int(bool(prior)), float(s2), float(eta)
+        c.max_batch, c.device = int(max_batch), int(device)
+        c.dropout, c.keep = int(bool(dropout)), float(keep)
+        self.cfg = c
+        self.Din, self.Dout, self.dropout = c.Din, c.Dout, bool(c.dropout)
+        self.h = _P()
+        check(self.lib.vaeb_clf_create(ctypes.byref(c), ctypes.byref(self.h)))
+        n = _I64()
+        check(self.lib.vaeb_clf_num_params(self.h, ctypes.byref(n)))
+        self.P = n.value
+
+    def close(self):
+        if getattr(self, "h", None) is not None and self.h.value:
+            self.lib.vaeb_clf_destroy(self.h)
+            self.h = _P()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_data(self, x, y):
+        x, y = np.ascontiguousarray(x, np.float32), np.ascontiguousarray(y, np.float32)
+        if x.ndim != 2 or y.ndim != 2 or x.shape[0] != y.shape[0] or x.shape[1] != self.Din or y.shape[1] != self.Dout:
+            raise VaebError(f"data shapes {x.shape}, {y.shape}: want [n x {self.Din}] and [n x {self.Dout}]")
+        check(self.lib.vaeb_clf_set_data(self.h, fptr(x), fptr(y), x.shape[0]))
+
+    def set_params(self, flat):
+        flat = np.ascontiguousarray(flat, np.float32)
+        check(self.lib.vaeb_clf_set_params(self.h, fptr(flat), flat.size))
+
+    def get_params(self):
+        out = np.empty(self.P, np.float32)
+        check(self.lib.vaeb_clf_get_params(self.h, fptr(out), out.size))
+        return out
+
+    def set_optimizer(self, rule, eta, beta1=0.0, beta2=0.0, eps=None):
+        """As AEContext.set_optimizer."""
+        if rule not in AE_RULE:
+            raise VaebError(f"rule {rule!r} not supported (adagrad | sga | adadelta | adam)")
+        o = AEOptimizerC(AE_RULE[rule], float(eta), float(beta1), float(beta2),
+                         float(AE_RULE_EPS[rule] if eps is None else eps))
+        check(self.lib.vaeb_clf_set_optimizer(self.h, ctypes.byref(o)))
+
+    def get_optimizer(self):
+        """(rule, eta, beta1, beta2, eps)."""
+        o = AEOptimizerC()
+        check(self.lib.vaeb_clf_get_optimizer(self.h, ctypes.byref(o)))
+        return AE_RULE_NAME[o.rule], o.eta, o.beta1, o.beta2, o.eps
+
+    def set_opt_state(self, slot, flat):
+        flat = np.ascontiguousarray(flat, np.float32)
+        check(self.lib.vaeb_clf_set_opt_state(self.h, int(slot), fptr(flat), flat.size))
+
+    def get_opt_state(self, slot):
+        out = np.empty(self.P, np.float32)
+        check(self.lib.vaeb_clf_get_opt_state(self.h, int(slot), fptr(out), out.size))
+        return out
+
+    # the AdaGrad accumulator under the names infalg's state arena uses
+    def set_adagrad_state(self, flat):
+        self.set_opt_state(0, flat)
+
+    def get_adagrad_state(self):
+        return self.get_opt_state(0)
+
+    def set_opt_step(self, t):
+        check(self.lib.vaeb_clf_set_opt_step(self.h, int(t)))
+
+    def get_opt_step(self):
+        n = _I64()
+        check(self.lib.vaeb_clf_get_opt_step(self.h, ctypes.byref(n)))
+        return n.value
+
+    def set_seed(self, seed):
+        check(self.lib.vaeb_clf_set_seed(self.h, int(seed)))
+
+    def set_step(self, step):
+        check(self.lib.vaeb_clf_set_step(self.h, int(step)))
+
+    def get_step(self):
+        n = _I64()
+        check(self.lib.vaeb_clf_get_step(self.h, ctypes.byref(n)))
+        return n.value
+
+    def train(self, idx):
+        """One step on the resident rows idx; the step's log-likelihood sum."""
+        idx = np.ascontiguousarray(idx, np.int32)
+        out = ctypes.c_float()
+        check(self.lib.vaeb_clf_train(self.h, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), idx.size,
+                                      ctypes.byref(out)))
+        return out.value
+
+    def train_many(self, idx, batch):
+        idx = np.ascontiguousarray(idx, np.int32)
+        out = np.empty(-(-idx.size // int(batch)), np.float32)
+        check(self.lib.vaeb_clf_train_many(self.h, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), idx.size,
+                                           int(batch), fptr(out)))
+        return out
+
+    def predict(self, x, draws=0):
+        """P [n x Dout]: softmax under theta (draws=0) or its mean over `draws` dropout draws."""
+        x = np.ascontiguousarray(x, np.float32)
+        out = np.empty((x.shape[0], self.Dout), np.float32)
+        check(self.lib.vaeb_clf_predict(self.h, fptr(x), x.shape[0], int(draws), fptr(out)))
+        return out
+
+    def loglik(self, x, y, draw=-1):
+        """The log-likelihood sum of (x, y) under theta (draw=-1) or under evaluation draw `draw`."""
+        x, y = np.ascontiguousarray(x, np.float32), np.ascontiguousarray(y, np.float32)
+        out = ctypes.c_double()
+        check(self.lib.vaeb_clf_loglik(self.h, fptr(x), fptr(y), x.shape[0], int(draw), ctypes.byref(out)))
+        return out.value
+
+    def accuracy(self, x, y, draws=0):
+        """Rows with y[i, argmax_j P_ij] == 1, counted on the device (an int)."""
+        x, y = np.ascontiguousarray(x, np.float32), np.ascontiguousarray(y, np.float32)
+        out = _I64()
+        check(self.lib.vaeb_clf_accuracy(self.h, fptr(x), fptr(y), x.shape[0], int(draws), ctypes.byref(out)))
+        return out.value
+
+    def draw_mask(self, step, draw=-1):
+        """The uint8 mask [P] of the training step at `step` (draw=-1) or of evaluation draw `draw`."""
+        out = np.empty(self.P, np.uint8)
+        check(self.lib.vaeb_clf_draw_mask(self.h, int(step), int(draw), out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
         return out

@@ -356,8 +356,16 @@ template <> struct AeRuleArgs<RULE_SGA> { float mu; };
 template <> struct AeRuleArgs<RULE_ADADELTA> { float* state1; float rho, eps; };
 template <> struct AeRuleArgs<RULE_ADAM> { float* state1; float b1, b2, eps, bc1, bc2; };
 
-template <int RULE>
-struct PAeWgradT : AeRuleArgs<RULE> {
+// Weight dropout (MASK, the classifier's dropout contexts; clf_softmax.hpp): the forward and the
+// data backward ran on theta~ = theta * m, so the gradient with respect to theta is m * C; the byte
+// mask m (indexed as theta) selects C or 0 before the prior term, and the rule updates the real
+// theta: a dropped element sees g = -theta / s2.  The argument and the select exist only in the
+// MASK instantiations (an empty base otherwise), so every other kernel is what it was.
+template <bool MASK> struct AeMaskArgs {};
+template <> struct AeMaskArgs<true> { const uint8_t* mask; };
+
+template <int RULE, bool MASK = false>
+struct PAeWgradT : AeRuleArgs<RULE>, AeMaskArgs<MASK> {
     Dbg a;
     int M, N, K;                     // M = Kin + 1, N = out width, K = batch rows
     const float* in; int ldin; int in_rows; const int* idx; int Kin;
@@ -397,7 +405,9 @@ struct PAeWgradT : AeRuleArgs<RULE> {
             if (m > Kin) continue;
             const int64_t i = (m == Kin) ? offb + n : offW + (int64_t)m * N + n;
             const float th = theta[i];
-            const float g = acc[0][r] - th * inv_s2;
+            float c = acc[0][r];
+            if constexpr (MASK) c = this->mask[i] ? c : 0.f;
+            const float g = c - th * inv_s2;
             if constexpr (RULE == RULE_SGA) {
                 const float v = this->mu * accum[i] + g;
                 accum[i] = v;

@@ -256,16 +256,45 @@ int ae_output(vaeb_ae* a, int M, AeOut what, const AeRows& y = AeRows{}) {
 // chosen by the block's base).  Adam's bias corrections are those of the step being enqueued,
 // t = opt_t + 1, formed in double: every step of a vaeb_ae_train_many carries its own.
 bool ae_two_slot(int rule) { return rule == VAEB_AE_RULE_ADADELTA || rule == VAEB_AE_RULE_ADAM; }
-void ae_put_rule(const vaeb_ae*, ae::AeRuleArgs<ae::RULE_ADAGRAD>&) {}
-void ae_put_rule(const vaeb_ae* a, ae::AeRuleArgs<ae::RULE_SGA>& q) { q.mu = a->opt.beta1; }
-void ae_put_rule(const vaeb_ae* a, ae::AeRuleArgs<ae::RULE_ADADELTA>& q) {
-    q.state1 = a->acc2; q.rho = a->opt.beta1; q.eps = a->opt.eps;
+// The optimiser of a layer-stack context as its launches see it: the rule and its numbers, the
+// steps taken and state slot 1 (vaeb_ae and vaeb_clf both hold these three).
+struct AeOptView { const vaeb_ae_optimizer& opt; int64_t opt_t; float* acc2; };
+void ae_put_rule(const AeOptView&, ae::AeRuleArgs<ae::RULE_ADAGRAD>&) {}
+void ae_put_rule(const AeOptView& a, ae::AeRuleArgs<ae::RULE_SGA>& q) { q.mu = a.opt.beta1; }
+void ae_put_rule(const AeOptView& a, ae::AeRuleArgs<ae::RULE_ADADELTA>& q) {
+    q.state1 = a.acc2; q.rho = a.opt.beta1; q.eps = a.opt.eps;
 }
-void ae_put_rule(const vaeb_ae* a, ae::AeRuleArgs<ae::RULE_ADAM>& q) {
-    const double t = (double)(a->opt_t + 1);
-    q.state1 = a->acc2; q.b1 = a->opt.beta1; q.b2 = a->opt.beta2; q.eps = a->opt.eps;
-    q.bc1 = (float)(1.0 - std::pow((double)a->opt.beta1, t));
-    q.bc2 = (float)(1.0 - std::pow((double)a->opt.beta2, t));
+void ae_put_rule(const AeOptView& a, ae::AeRuleArgs<ae::RULE_ADAM>& q) {
+    const double t = (double)(a.opt_t + 1);
+    q.state1 = a.acc2; q.b1 = a.opt.beta1; q.b2 = a.opt.beta2; q.eps = a.opt.eps;
+    q.bc1 = (float)(1.0 - std::pow((double)a.opt.beta1, t));
+    q.bc2 = (float)(1.0 - std::pow((double)a.opt.beta2, t));
+}
+
+// Why a vaeb_ae_optimizer is not valid, or nullptr (the rules of vaeb_ae_set_optimizer).
+const char* ae_opt_why(const vaeb_ae_optimizer* o) {
+    auto unit = [](float b) { return b >= 0.f && b < 1.f; };   // NaN fails
+    if (!(o->eta > 0.f) || !std::isfinite(o->eta)) return "eta must be finite and > 0";
+    switch (o->rule) {
+    case VAEB_AE_RULE_ADAGRAD:
+        if (o->eps != 1e-6f) return "AdaGrad's eps is 1e-6 (the kernel's literal)";
+        if (o->beta1 != 0.f || o->beta2 != 0.f) return "AdaGrad uses no beta: beta1 and beta2 must be 0";
+        return nullptr;
+    case VAEB_AE_RULE_SGA:
+        if (!unit(o->beta1)) return "the momentum (beta1) must be in [0, 1)";
+        if (o->beta2 != 0.f || o->eps != 0.f) return "gradient ascent uses beta1 alone: beta2 and eps must be 0";
+        return nullptr;
+    case VAEB_AE_RULE_ADADELTA:
+        if (!unit(o->beta1) || o->beta1 == 0.f) return "rho (beta1) must be in (0, 1)";
+        if (!(o->eps > 0.f) || !std::isfinite(o->eps)) return "eps must be finite and > 0";
+        if (o->beta2 != 0.f) return "AdaDelta uses no beta2: it must be 0";
+        return nullptr;
+    case VAEB_AE_RULE_ADAM:
+        if (!unit(o->beta1) || !unit(o->beta2)) return "beta1 and beta2 must be in [0, 1)";
+        if (!(o->eps > 0.f) || !std::isfinite(o->eps)) return "eps must be finite and > 0";
+        return nullptr;
+    }
+    return "rule must be VAEB_AE_RULE_ADAGRAD | _SGA | _ADADELTA | _ADAM";
 }
 
 // One weight-gradient + update launch for layer l from its input in (gathered through in.idx for
@@ -278,7 +307,7 @@ int ae_wgrad(vaeb_ae* a, const AeLayer& l, const AeRows& in, const float* dout, 
         p.dout = dout;
         p.theta = a->theta; p.accum = a->acc; p.offW = l.oW; p.offb = l.ob;
         p.eta = a->opt.eta; p.inv_s2 = 1.0f / a->c.s2;
-        ae_put_rule(a, p);
+        ae_put_rule(AeOptView{a->opt, a->opt_t, a->acc2}, p);
         launch_bigk<1>(a->s, p);
     };
     switch (a->opt.rule) {
@@ -497,12 +526,61 @@ int ae_predict(vaeb_ae* a, const float* x, int64_t n, float* out, AePredict what
     });
 }
 
-int ae_xfer(vaeb_ae* a, float* dev, const float* hin, float* hout, int64_t n) {
+// The optimiser state and arena transfers of a layer-stack context, shared by vaeb_ae and vaeb_clf:
+// both hold P, s, mem, acc, acc2, opt and opt_t under these names.
+template <class Ctx>
+int ae_xfer(Ctx* a, float* dev, const float* hin, float* hout, int64_t n) {
     if (!a || (!hin && !hout)) return fail(VAEB_ERR_ARG, "null argument");
     if (n != a->P) return fail(VAEB_ERR_ARG, "size mismatch: got %lld, expected %lld", (long long)n, (long long)a->P);
     HIP_TRY(hipStreamSynchronize(a->s));
     if (hin) HIP_TRY(hipMemcpy(dev, hin, sizeof(float) * n, hipMemcpyHostToDevice));
     else HIP_TRY(hipMemcpy(hout, dev, sizeof(float) * n, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// vaeb_ae_set_optimizer's body.  The fields a rule does not use are 0 (AdaGrad's eps: the kernel's
+// literal 1e-6).
+template <class Ctx>
+int ae_set_optimizer(Ctx* a, const vaeb_ae_optimizer* o) {
+    if (!a || !o) return fail(VAEB_ERR_ARG, "null argument");
+    const char* why = ae_opt_why(o);
+    if (why)
+        return fail(VAEB_ERR_ARG, "optimizer {rule %d, eta %g, beta1 %g, beta2 %g, eps %g}: %s", o->rule, (double)o->eta,
+                    (double)o->beta1, (double)o->beta2, (double)o->eps, why);
+    if (o->rule != a->opt.rule) {   // another rule: its state starts from zero, after the enqueued steps
+        if (ae_two_slot(o->rule))
+            if (int rc = a->mem.lazy(&a->acc2, a->P)) return rc;
+        HIP_TRY(hipMemsetAsync(a->acc, 0, sizeof(float) * (size_t)a->P, a->s));
+        if (a->acc2) HIP_TRY(hipMemsetAsync(a->acc2, 0, sizeof(float) * (size_t)a->P, a->s));
+        a->opt_t = 0;
+    }
+    a->opt = *o;   // launch arguments: the enqueued steps keep theirs
+    return 0;
+}
+
+template <class Ctx>
+float* ae_opt_slot(Ctx* a, int32_t slot) {
+    if (!a) return nullptr;
+    if (slot == 0) return a->acc;
+    if (slot == 1 && ae_two_slot(a->opt.rule)) return a->acc2;
+    fail(VAEB_ERR_ARG, "optimizer state slot %d: rule %d has slot 0%s", slot, a->opt.rule,
+         ae_two_slot(a->opt.rule) ? " and slot 1" : " only");
+    return nullptr;
+}
+
+// set / get of state slot `slot` (hin or hout set)
+template <class Ctx>
+int ae_opt_state(Ctx* a, int32_t slot, const float* hin, float* hout, int64_t n) {
+    if (!a || (!hin && !hout)) return fail(VAEB_ERR_ARG, "null argument");
+    float* dev = ae_opt_slot(a, slot);
+    return dev ? ae_xfer(a, dev, hin, hout, n) : VAEB_ERR_ARG;
+}
+
+template <class Ctx>
+int ae_set_opt_step(Ctx* a, int64_t t) {
+    if (!a) return fail(VAEB_ERR_ARG, "null argument");
+    if (t < 0) return fail(VAEB_ERR_ARG, "optimizer step %lld < 0", (long long)t);
+    a->opt_t = t;
     return 0;
 }
 
@@ -635,45 +713,7 @@ int vaeb_ae_set_adagrad_state(vaeb_ae* a, const float* f, int64_t n) { return ae
 int vaeb_ae_get_adagrad_state(vaeb_ae* a, float* f, int64_t n) { return ae_xfer(a, a ? a->acc : nullptr, nullptr, f, n); }
 
 // ------------------------------------------------------------------ the update rule
-// The fields a rule does not use are 0 (AdaGrad's eps: the kernel's literal 1e-6).
-int vaeb_ae_set_optimizer(vaeb_ae* a, const vaeb_ae_optimizer* o) {
-    if (!a || !o) return fail(VAEB_ERR_ARG, "null argument");
-    auto unit = [](float b) { return b >= 0.f && b < 1.f; };   // NaN fails
-    const char* why = nullptr;
-    if (!(o->eta > 0.f) || !std::isfinite(o->eta)) why = "eta must be finite and > 0";
-    else switch (o->rule) {
-    case VAEB_AE_RULE_ADAGRAD:
-        if (o->eps != 1e-6f) why = "AdaGrad's eps is 1e-6 (the kernel's literal)";
-        else if (o->beta1 != 0.f || o->beta2 != 0.f) why = "AdaGrad uses no beta: beta1 and beta2 must be 0";
-        break;
-    case VAEB_AE_RULE_SGA:
-        if (!unit(o->beta1)) why = "the momentum (beta1) must be in [0, 1)";
-        else if (o->beta2 != 0.f || o->eps != 0.f) why = "gradient ascent uses beta1 alone: beta2 and eps must be 0";
-        break;
-    case VAEB_AE_RULE_ADADELTA:
-        if (!unit(o->beta1) || o->beta1 == 0.f) why = "rho (beta1) must be in (0, 1)";
-        else if (!(o->eps > 0.f) || !std::isfinite(o->eps)) why = "eps must be finite and > 0";
-        else if (o->beta2 != 0.f) why = "AdaDelta uses no beta2: it must be 0";
-        break;
-    case VAEB_AE_RULE_ADAM:
-        if (!unit(o->beta1) || !unit(o->beta2)) why = "beta1 and beta2 must be in [0, 1)";
-        else if (!(o->eps > 0.f) || !std::isfinite(o->eps)) why = "eps must be finite and > 0";
-        break;
-    default: why = "rule must be VAEB_AE_RULE_ADAGRAD | _SGA | _ADADELTA | _ADAM";
-    }
-    if (why)
-        return fail(VAEB_ERR_ARG, "optimizer {rule %d, eta %g, beta1 %g, beta2 %g, eps %g}: %s", o->rule, (double)o->eta,
-                    (double)o->beta1, (double)o->beta2, (double)o->eps, why);
-    if (o->rule != a->opt.rule) {   // another rule: its state starts from zero, after the enqueued steps
-        if (ae_two_slot(o->rule))
-            if (int rc = a->mem.lazy(&a->acc2, a->P)) return rc;
-        HIP_TRY(hipMemsetAsync(a->acc, 0, sizeof(float) * (size_t)a->P, a->s));
-        if (a->acc2) HIP_TRY(hipMemsetAsync(a->acc2, 0, sizeof(float) * (size_t)a->P, a->s));
-        a->opt_t = 0;
-    }
-    a->opt = *o;   // launch arguments: the enqueued steps keep theirs
-    return 0;
-}
+int vaeb_ae_set_optimizer(vaeb_ae* a, const vaeb_ae_optimizer* o) { return ae_set_optimizer(a, o); }
 
 int vaeb_ae_get_optimizer(vaeb_ae* a, vaeb_ae_optimizer* o) {
     if (!a || !o) return fail(VAEB_ERR_ARG, "null argument");
@@ -681,33 +721,9 @@ int vaeb_ae_get_optimizer(vaeb_ae* a, vaeb_ae_optimizer* o) {
     return 0;
 }
 
-static float* ae_opt_slot(vaeb_ae* a, int32_t slot) {
-    if (!a) return nullptr;
-    if (slot == 0) return a->acc;
-    if (slot == 1 && ae_two_slot(a->opt.rule)) return a->acc2;
-    fail(VAEB_ERR_ARG, "optimizer state slot %d: rule %d has slot 0%s", slot, a->opt.rule,
-         ae_two_slot(a->opt.rule) ? " and slot 1" : " only");
-    return nullptr;
-}
-
-int vaeb_ae_set_opt_state(vaeb_ae* a, int32_t slot, const float* f, int64_t n) {
-    if (!a || !f) return fail(VAEB_ERR_ARG, "null argument");
-    float* dev = ae_opt_slot(a, slot);
-    return dev ? ae_xfer(a, dev, f, nullptr, n) : VAEB_ERR_ARG;
-}
-
-int vaeb_ae_get_opt_state(vaeb_ae* a, int32_t slot, float* f, int64_t n) {
-    if (!a || !f) return fail(VAEB_ERR_ARG, "null argument");
-    float* dev = ae_opt_slot(a, slot);
-    return dev ? ae_xfer(a, dev, nullptr, f, n) : VAEB_ERR_ARG;
-}
-
-int vaeb_ae_set_opt_step(vaeb_ae* a, int64_t t) {
-    if (!a) return fail(VAEB_ERR_ARG, "null argument");
-    if (t < 0) return fail(VAEB_ERR_ARG, "optimizer step %lld < 0", (long long)t);
-    a->opt_t = t;
-    return 0;
-}
+int vaeb_ae_set_opt_state(vaeb_ae* a, int32_t slot, const float* f, int64_t n) { return ae_opt_state(a, slot, f, nullptr, n); }
+int vaeb_ae_get_opt_state(vaeb_ae* a, int32_t slot, float* f, int64_t n) { return ae_opt_state(a, slot, nullptr, f, n); }
+int vaeb_ae_set_opt_step(vaeb_ae* a, int64_t t) { return ae_set_opt_step(a, t); }
 
 int vaeb_ae_get_opt_step(vaeb_ae* a, int64_t* t) {
     if (!a || !t) return fail(VAEB_ERR_ARG, "null argument");

@@ -47,6 +47,7 @@
 #include "ae_iwae.hpp"
 #include "ae_corrupt.hpp"
 #include "ae_codes.hpp"
+#include "clf_softmax.hpp"
 
 using namespace vaeb;
 
@@ -1723,3 +1724,4 @@ int vaeb_kernel_name(int32_t id, char* out, int32_t cap) {
 
 // degenerate-vae autoencoder (vaeb_ae_*) on the same fp32 tile engine
 #include "engine_ae.inc"
+#include "engine_clf.inc"
