@@ -144,3 +144,35 @@ def test_construct_ae_mirror_learns():
     assert ae.rmse(X, reconstruct(X)) < ae.rmse(X, np.zeros_like(X))
     z = encode(X[:7])
     assert z.shape == (7, 5) and decode(z).shape == (7, 784)
+
+
+def test_train_error_codes_and_texts():
+    """The argument checks of vaeb_ae_train(_many) on a live 20-(8)-3-(8) context of max_batch 8, in
+    their order: the code and the vaeb_last_error text of each (the texts as engine_ae.inc had them
+    when the checks were its own; they are the shared training driver's now).  No kernel is launched."""
+    import ctypes
+    from vaeb_amd import _lib
+    ctx = _lib.AEContext(20, (8,), 3, (8,), max_batch=8)
+    try:
+        L, h = ctx.lib, ctx.h
+        I32 = ctypes.POINTER(ctypes.c_int32)
+        out = np.zeros(4, np.float32)
+
+        def call(fn, idx, *batch):
+            idx = np.asarray(idx, np.int32)
+            rc = fn(h, idx.ctypes.data_as(I32), idx.size, *batch, _lib.fptr(out))
+            return rc, L.vaeb_last_error().decode()
+
+        nine = np.arange(9)
+        assert call(L.vaeb_ae_train_many, nine, 9) == (-1, "batch 9 > max_batch 8")        # before the data check
+        assert call(L.vaeb_ae_train, nine) == (-1, "batch 9 > max_batch 8")
+        assert call(L.vaeb_ae_train_many, nine, 0) == (-1, "bad arguments")
+        assert call(L.vaeb_ae_train_many, nine, 8) == (-3, "vaeb_ae_set_data has not been called")
+        assert call(L.vaeb_ae_train, [0]) == (-3, "vaeb_ae_set_data has not been called")
+        ctx.set_data(np.zeros((12, 20), np.float32))
+        assert call(L.vaeb_ae_train_many, [0, 12], 2) == (-1, "row index 12 out of range [0, 12)")
+        assert call(L.vaeb_ae_train, [3, -1]) == (-1, "row index -1 out of range [0, 12)")
+        assert call(L.vaeb_ae_train_many, nine, 9) == (-1, "batch 9 > max_batch 8")
+        assert ctx.get_opt_step() == 0 and not ctx.get_params().any() and not ctx.get_opt_state(0).any()
+    finally:
+        ctx.close()

@@ -633,7 +633,99 @@ class Context:
         return out
 
 
-class AEContext:
+class _StackContext:
+    """What the handles of the layer-stack engine share (AEContext, CLFContext): the library calls
+    <prefix>destroy, num_params, set_params / get_params, the six optimiser calls, train and
+    train_many, with prefix "vaeb_ae_" or "vaeb_clf_"."""
+
+    def __init__(self, prefix):
+        self.lib = load()
+        self._prefix = prefix
+
+    def _call(self, name, *args):
+        check(getattr(self.lib, self._prefix + name)(self.h, *args))
+
+    def _create(self, cfg):
+        """<prefix>create(cfg) into self.h, then P."""
+        self.h = _P()
+        check(getattr(self.lib, self._prefix + "create")(ctypes.byref(cfg), ctypes.byref(self.h)))
+        n = _I64()
+        self._call("num_params", ctypes.byref(n))
+        self.P = n.value
+
+    def close(self):
+        if getattr(self, "h", None) is not None and self.h.value:
+            getattr(self.lib, self._prefix + "destroy")(self.h)
+            self.h = _P()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_params(self, flat):
+        flat = np.ascontiguousarray(flat, np.float32)
+        self._call("set_params", fptr(flat), flat.size)
+
+    def get_params(self):
+        out = np.empty(self.P, np.float32)
+        self._call("get_params", fptr(out), out.size)
+        return out
+
+    # ---- the update rule (vaeb_ae_set_optimizer; a fresh context: adagrad at the constructor's eta)
+    def set_optimizer(self, rule, eta, beta1=0.0, beta2=0.0, eps=None):
+        """rule: "adagrad" | "sga" | "adadelta" | "adam"; beta1 is the momentum (sga), rho (adadelta)
+        or beta1 (adam), beta2 adam's; eps None: the rule's default (adagrad's fixed 1e-6, sga 0,
+        adadelta 1e-6, adam 1e-8).  Another rule than the current one zeroes the optimiser state and
+        step; the same rule changes the numbers only (a step-size schedule)."""
+        if rule not in AE_RULE:
+            raise VaebError(f"rule {rule!r} not supported (adagrad | sga | adadelta | adam)")
+        o = AEOptimizerC(AE_RULE[rule], float(eta), float(beta1), float(beta2),
+                         float(AE_RULE_EPS[rule] if eps is None else eps))
+        self._call("set_optimizer", ctypes.byref(o))
+
+    def get_optimizer(self):
+        """(rule, eta, beta1, beta2, eps)."""
+        o = AEOptimizerC()
+        self._call("get_optimizer", ctypes.byref(o))
+        return AE_RULE_NAME[o.rule], o.eta, o.beta1, o.beta2, o.eps
+
+    def set_opt_state(self, slot, flat):
+        flat = np.ascontiguousarray(flat, np.float32)
+        self._call("set_opt_state", int(slot), fptr(flat), flat.size)
+
+    def get_opt_state(self, slot):
+        """Slot 0 (adagrad's accumulator, sga's velocity, adadelta's g_ac, adam's m) or slot 1
+        (adadelta's dx_ac, adam's v), flat in theta order."""
+        out = np.empty(self.P, np.float32)
+        self._call("get_opt_state", int(slot), fptr(out), out.size)
+        return out
+
+    def set_opt_step(self, t):
+        self._call("set_opt_step", int(t))
+
+    def get_opt_step(self):
+        """Optimiser steps taken since the rule was set (adam's t of the last step)."""
+        n = _I64()
+        self._call("get_opt_step", ctypes.byref(n))
+        return n.value
+
+    def train(self, idx):
+        """One step on the resident rows idx; the step's value (CLFContext: its log-likelihood sum)."""
+        idx = np.ascontiguousarray(idx, np.int32)
+        out = ctypes.c_float()
+        self._call("train", idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), idx.size, ctypes.byref(out))
+        return out.value
+
+    def train_many(self, idx, batch):
+        idx = np.ascontiguousarray(idx, np.int32)
+        out = np.empty(-(-idx.size // int(batch)), np.float32)
+        self._call("train_many", idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), idx.size, int(batch), fptr(out))
+        return out
+
+
+class AEContext(_StackContext):
     """One degenerate-vae autoencoder (vaeb_ae_*) on one GPU; latent="gauss": the deep VAE on
     the same layer stack (include/vaeb_hip.h enum vaeb_ae_latent); iw_samples = K >= 2: train on
     the K-sample importance-weighted bound (K * len(idx) <= max_batch per step).  otype="se" with
@@ -649,7 +741,7 @@ class AEContext:
 
     def __init__(self, Dobs, Denc, Dz, Ddec, otype="binary", act="tanh", s2=1.0, eta=0.01, max_batch=100,
                  device=0, latent="point", iw_samples=1, corruption="none", prior="normal"):
-        self.lib = load()
+        super().__init__("vaeb_ae_")
         c = AEConfigC()
         c.Dobs, c.Dz = int(Dobs), int(Dz)
         Denc, Ddec = list(Denc), list(Ddec)
@@ -681,35 +773,11 @@ class AEContext:
         self.prior = prior
         self.cfg = c
         self.Dobs, self.Dz = c.Dobs, c.Dz
-        self.h = _P()
-        check(self.lib.vaeb_ae_create(ctypes.byref(c), ctypes.byref(self.h)))
-        n = _I64()
-        check(self.lib.vaeb_ae_num_params(self.h, ctypes.byref(n)))
-        self.P = n.value
-
-    def close(self):
-        if getattr(self, "h", None) is not None and self.h.value:
-            self.lib.vaeb_ae_destroy(self.h)
-            self.h = _P()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(c)
 
     def set_data(self, x):
         x = np.ascontiguousarray(x, np.float32)
         check(self.lib.vaeb_ae_set_data(self.h, fptr(x), x.shape[0]))
-
-    def set_params(self, flat):
-        flat = np.ascontiguousarray(flat, np.float32)
-        check(self.lib.vaeb_ae_set_params(self.h, fptr(flat), flat.size))
-
-    def get_params(self):
-        out = np.empty(self.P, np.float32)
-        check(self.lib.vaeb_ae_get_params(self.h, fptr(out), out.size))
-        return out
 
     def set_adagrad_state(self, flat):
         flat = np.ascontiguousarray(flat, np.float32)
@@ -718,59 +786,6 @@ class AEContext:
     def get_adagrad_state(self):
         out = np.empty(self.P, np.float32)
         check(self.lib.vaeb_ae_get_adagrad_state(self.h, fptr(out), out.size))
-        return out
-
-    # ---- the update rule (vaeb_ae_set_optimizer; a fresh context: adagrad at the constructor's eta)
-    def set_optimizer(self, rule, eta, beta1=0.0, beta2=0.0, eps=None):
-        """rule: "adagrad" | "sga" | "adadelta" | "adam"; beta1 is the momentum (sga), rho (adadelta)
-        or beta1 (adam), beta2 adam's; eps None: the rule's default (adagrad's fixed 1e-6, sga 0,
-        adadelta 1e-6, adam 1e-8).  Another rule than the current one zeroes the optimiser state and
-        step; the same rule changes the numbers only (a step-size schedule)."""
-        if rule not in AE_RULE:
-            raise VaebError(f"rule {rule!r} not supported (adagrad | sga | adadelta | adam)")
-        o = AEOptimizerC(AE_RULE[rule], float(eta), float(beta1), float(beta2),
-                         float(AE_RULE_EPS[rule] if eps is None else eps))
-        check(self.lib.vaeb_ae_set_optimizer(self.h, ctypes.byref(o)))
-
-    def get_optimizer(self):
-        """(rule, eta, beta1, beta2, eps)."""
-        o = AEOptimizerC()
-        check(self.lib.vaeb_ae_get_optimizer(self.h, ctypes.byref(o)))
-        return AE_RULE_NAME[o.rule], o.eta, o.beta1, o.beta2, o.eps
-
-    def set_opt_state(self, slot, flat):
-        flat = np.ascontiguousarray(flat, np.float32)
-        check(self.lib.vaeb_ae_set_opt_state(self.h, int(slot), fptr(flat), flat.size))
-
-    def get_opt_state(self, slot):
-        """Slot 0 (adagrad's accumulator, sga's velocity, adadelta's g_ac, adam's m) or slot 1
-        (adadelta's dx_ac, adam's v), flat in theta order."""
-        out = np.empty(self.P, np.float32)
-        check(self.lib.vaeb_ae_get_opt_state(self.h, int(slot), fptr(out), out.size))
-        return out
-
-    def set_opt_step(self, t):
-        check(self.lib.vaeb_ae_set_opt_step(self.h, int(t)))
-
-    def get_opt_step(self):
-        """Optimiser steps taken since the rule was set (adam's t of the last step)."""
-        n = _I64()
-        check(self.lib.vaeb_ae_get_opt_step(self.h, ctypes.byref(n)))
-        return n.value
-
-    def train(self, idx):
-        idx = np.ascontiguousarray(idx, np.int32)
-        out = ctypes.c_float()
-        check(self.lib.vaeb_ae_train(self.h, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), idx.size,
-                                     ctypes.byref(out)))
-        return out.value
-
-    def train_many(self, idx, batch):
-        idx = np.ascontiguousarray(idx, np.int32)
-        nb = -(-idx.size // int(batch))
-        out = np.empty(nb, np.float32)
-        check(self.lib.vaeb_ae_train_many(self.h, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), idx.size,
-                                          int(batch), fptr(out)))
         return out
 
     def _predict(self, fn, x, width_out):
@@ -893,7 +908,7 @@ class AEContext:
         return out
 
 
-class CLFContext:
+class CLFContext(_StackContext):
     """One softmax MLP classifier (vaeb_clf_*) on one GPU: tanh / sigmoid / relu hidden layers, a
     softmax output scored by loss="bernoulli" (the reference's mlp.py:112) or "categorical",
     prior=True for the N(0, s2) prior on theta (the reference leaves it out), dropout=True for weight
@@ -903,7 +918,7 @@ class CLFContext:
 
     def __init__(self, Din, Dh, Dout, act="tanh", loss="bernoulli", prior=False, s2=1.0, eta=0.01, max_batch=100,
                  device=0, dropout=False, keep=0.5):
-        self.lib = load()
+        super().__init__("vaeb_clf_")
         c = CLFConfigC()
         Dh = list(Dh)
         if not 1 <= len(Dh) <= AE_MAX_LAYERS:
@@ -919,22 +934,7 @@ class CLFContext:
         c.dropout, c.keep = int(bool(dropout)), float(keep)
         self.cfg = c
         self.Din, self.Dout, self.dropout = c.Din, c.Dout, bool(c.dropout)
-        self.h = _P()
-        check(self.lib.vaeb_clf_create(ctypes.byref(c), ctypes.byref(self.h)))
-        n = _I64()
-        check(self.lib.vaeb_clf_num_params(self.h, ctypes.byref(n)))
-        self.P = n.value
-
-    def close(self):
-        if getattr(self, "h", None) is not None and self.h.value:
-            self.lib.vaeb_clf_destroy(self.h)
-            self.h = _P()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(c)
 
     def set_data(self, x, y):
         x, y = np.ascontiguousarray(x, np.float32), np.ascontiguousarray(y, np.float32)
@@ -942,52 +942,12 @@ class CLFContext:
             raise VaebError(f"data shapes {x.shape}, {y.shape}: want [n x {self.Din}] and [n x {self.Dout}]")
         check(self.lib.vaeb_clf_set_data(self.h, fptr(x), fptr(y), x.shape[0]))
 
-    def set_params(self, flat):
-        flat = np.ascontiguousarray(flat, np.float32)
-        check(self.lib.vaeb_clf_set_params(self.h, fptr(flat), flat.size))
-
-    def get_params(self):
-        out = np.empty(self.P, np.float32)
-        check(self.lib.vaeb_clf_get_params(self.h, fptr(out), out.size))
-        return out
-
-    def set_optimizer(self, rule, eta, beta1=0.0, beta2=0.0, eps=None):
-        """As AEContext.set_optimizer."""
-        if rule not in AE_RULE:
-            raise VaebError(f"rule {rule!r} not supported (adagrad | sga | adadelta | adam)")
-        o = AEOptimizerC(AE_RULE[rule], float(eta), float(beta1), float(beta2),
-                         float(AE_RULE_EPS[rule] if eps is None else eps))
-        check(self.lib.vaeb_clf_set_optimizer(self.h, ctypes.byref(o)))
-
-    def get_optimizer(self):
-        """(rule, eta, beta1, beta2, eps)."""
-        o = AEOptimizerC()
-        check(self.lib.vaeb_clf_get_optimizer(self.h, ctypes.byref(o)))
-        return AE_RULE_NAME[o.rule], o.eta, o.beta1, o.beta2, o.eps
-
-    def set_opt_state(self, slot, flat):
-        flat = np.ascontiguousarray(flat, np.float32)
-        check(self.lib.vaeb_clf_set_opt_state(self.h, int(slot), fptr(flat), flat.size))
-
-    def get_opt_state(self, slot):
-        out = np.empty(self.P, np.float32)
-        check(self.lib.vaeb_clf_get_opt_state(self.h, int(slot), fptr(out), out.size))
-        return out
-
     # the AdaGrad accumulator under the names infalg's state arena uses
     def set_adagrad_state(self, flat):
         self.set_opt_state(0, flat)
 
     def get_adagrad_state(self):
         return self.get_opt_state(0)
-
-    def set_opt_step(self, t):
-        check(self.lib.vaeb_clf_set_opt_step(self.h, int(t)))
-
-    def get_opt_step(self):
-        n = _I64()
-        check(self.lib.vaeb_clf_get_opt_step(self.h, ctypes.byref(n)))
-        return n.value
 
     def set_seed(self, seed):
         check(self.lib.vaeb_clf_set_seed(self.h, int(seed)))
@@ -999,21 +959,6 @@ class CLFContext:
         n = _I64()
         check(self.lib.vaeb_clf_get_step(self.h, ctypes.byref(n)))
         return n.value
-
-    def train(self, idx):
-        """One step on the resident rows idx; the step's log-likelihood sum."""
-        idx = np.ascontiguousarray(idx, np.int32)
-        out = ctypes.c_float()
-        check(self.lib.vaeb_clf_train(self.h, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), idx.size,
-                                      ctypes.byref(out)))
-        return out.value
-
-    def train_many(self, idx, batch):
-        idx = np.ascontiguousarray(idx, np.int32)
-        out = np.empty(-(-idx.size // int(batch)), np.float32)
-        check(self.lib.vaeb_clf_train_many(self.h, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), idx.size,
-                                           int(batch), fptr(out)))
-        return out
 
     def predict(self, x, draws=0):
         """P [n x Dout]: softmax under theta (draws=0) or its mean over `draws` dropout draws."""

@@ -1,5 +1,5 @@
 // dev_owner.hpp -- the one owner of a context's device memory (host code only).  vaeb_ctx,
-// vaeb_ae and h16c::BfState each hold a DevOwner; every buffer is registered where it is
+// vaeb_ae and vaeb_clf (through their StackCore) and h16c::BfState each hold a DevOwner; every buffer is registered where it is
 // allocated and release_all frees the list, so no second list has to be kept in step with the
 // allocations.  Interior pointers (a second array inside one block) are never registered.
 #pragma once

@@ -1,7 +1,10 @@
 // engine_ae.inc -- the layer-stack engine (include/vaeb_hip.h vaeb_ae_*): the autoencoders and
 // deep VAEs on the fp32 tile engine's kernels (ae_mlp.hpp, ae_iwae.hpp).  Included by
-// vaeb_hip.hip after the VAEB helpers.  Each call and the helper sequence it runs:
-//   vaeb_ae_train(_many)  per batch ae_step: ae_encode | ae_decode_hidden | ae_output(TRAIN) | the value
+// vaeb_hip.hip after stack_core.inc: vaeb_ae is a StackCore, and the launches of the plain forward
+// layers, of every data gradient and of every update, the update rule's calls, the training
+// driver, the chunk loop (ae_chunks: core_chunks on xin) and the chunk sum are the core's.
+// Each call and the helper sequence it runs:
+//   vaeb_ae_train(_many)  core_train_many, per batch ae_step: ae_encode | ae_decode_hidden | ae_output(TRAIN) | the value
 //                         (iw_samples >= 2: ae_iw_forward instead), then ae_bwd_decoder | ae_bwd_encoder;
 //                         on a corrupting context ae_corrupt_rows first: ae_encode and ae_bwd_encoder read
 //                         its xt, everything else the clean rows
@@ -10,51 +13,41 @@
 //   vaeb_ae_encode        ae_chunks: ae_encode (zero noise)
 //   vaeb_ae_decode        ae_chunks: ae_decode_hidden on the caller's z | ae_output(PREDICT)
 //   vaeb_ae_sq_error      ae_chunks: ae_encode (zero noise) | ae_decode_hidden | ae_output(SQ) |
-//                         ae_row_sum_kernel | ae_sum_to_host
+//                         ae_row_sum_kernel | core_sum_to_host
 //   vaeb_ae_encode_dist   ae_chunks: ae_encode (evaluation noise when z is wanted)
 //   vaeb_ae_elbo          ae_chunks: ae_encode (evaluation noise) | ae_decode_hidden | ae_output(TRAIN) |
-//                         ae_elbo_kernel | ae_sum_to_host
+//                         ae_elbo_kernel | core_sum_to_host
 //   vaeb_ae_marginal_ll   ae_chunks: ae_encode (zero noise), per pass of sample planes ae_iw_sample_kernel |
-//                         ae_decode_hidden | ae_output(VALUE) | iw_lse_kernel, then ae_sum_to_host
+//                         ae_decode_hidden | ae_output(VALUE) | iw_lse_kernel, then core_sum_to_host
 //   vaeb_ae_encode_bits   ae_chunks: ae_encode (zero noise) | ae_pack_bits_kernel
 //   vaeb_ae_decode_bits   ae_chunks: ae_unpack_bits_kernel | ae_decode_hidden | ae_output(PREDICT)
-//   vaeb_ae_set_optimizer the rule and hyper-parameters ae_wgrad launches with (PAeWgradT<RULE>, a host
-//                         switch there and nowhere else); another rule: both state slots and the
-//                         optimiser step counter zeroed on the stream
+//   vaeb_ae_set_optimizer core_set_optimizer: the rule and hyper-parameters core_wgrad launches with
+//                         (PAeWgradT<RULE>); another rule: both state slots and the optimiser step
+//                         counter zeroed on the stream
 // A context of the two-mode latent prior (c.prior, ae_two_mode) runs the same sequences with the TM
 // instantiations of the latent forward, the decoder's first-layer backward and the sample kernel;
 // every other context launches what it launched before.
 // vaeb_ae_create lays theta out (an AeLayer per layer and head); device memory is the context's:
-// vaeb_ae::mem (dev_owner.hpp) registers every buffer where it is allocated, vaeb_ae_destroy releases it.
-
-// One affine map of theta: W [K x N] at theta + oW, b [N] at theta + ob.
-struct AeLayer { int K, N; int64_t oW, ob; };
+// StackCore::mem (dev_owner.hpp) registers every buffer where it is allocated, core_close releases it.
 
 // A layer of one or two heads on the same input (the latent: Wz, or Wzmu and Wzlv; the output:
 // Wout, or Wmu and Wlogs2) with the deltas of the heads' pre-activations.
 struct AeHeads { int n; AeLayer l[2]; float* d[2]; };
 
-struct vaeb_ae {
+struct vaeb_ae : StackCore {
     vaeb_ae_config c{};
-    hipStream_t s = nullptr;
-    int64_t P = 0;
     AeLayer enc[VAEB_AE_MAX_LAYERS] = {}, dec[VAEB_AE_MAX_LAYERS] = {};   // Dobs -> Denc..., Dz -> Ddec...
     AeHeads lat{}, out{};             // d: dZ, or dmu and dlv (Gaussian latent); dA (and dA2, cont)
-    DevOwner mem;                     // every device allocation; released by vaeb_ae_destroy
-    float *theta = nullptr, *acc = nullptr;
     float* data = nullptr;
     int64_t nrows = 0;
-    int* idx = nullptr;               // device index list (epoch capacity)
-    int64_t idx_cap = 0;
     // activations / deltas per layer (H[0], G[0] unused)
     float *H[VAEB_AE_MAX_LAYERS + 1] = {}, *G[VAEB_AE_MAX_LAYERS + 1] = {};
     float *dH[VAEB_AE_MAX_LAYERS + 1] = {}, *dG[VAEB_AE_MAX_LAYERS + 1] = {};
     float *Z = nullptr, *dZ = nullptr, *Xpr = nullptr, *ls2 = nullptr, *dA = nullptr, *dA2 = nullptr;
-    float *ll = nullptr, *outs = nullptr, *xin = nullptr;
-    int64_t outs_cap = 0;
+    float *ll = nullptr, *xin = nullptr;
     // Gaussian latent (c.latent == VAEB_AE_LATENT_GAUSS): a->Z holds z
     float *mu = nullptr, *lv = nullptr, *dmu = nullptr, *dlv = nullptr, *kl = nullptr;
-    double* esum = nullptr;           // vaeb_ae_elbo / vaeb_ae_marginal_ll / vaeb_ae_sq_error: one chunk's sum
+    // esum (the core's): vaeb_ae_elbo / vaeb_ae_marginal_ll / vaeb_ae_sq_error, one chunk's sum
     float* sq_rows = nullptr;         // vaeb_ae_sq_error: a chunk's row values [max_batch] (first use)
     // vaeb_ae_marginal_ll scratch (allocated on first use): latent terms [max_batch], running
     // (max, sum) [2 max_batch], row values [max_batch]; the observation row of each stacked row
@@ -82,12 +75,6 @@ struct vaeb_ae {
     // arguments as the level above; a chunk's code words [max_batch x ceil(Dz / 32)] (first use)
     float pr_mean1 = 1.f, pr_width = 0.25f;
     uint32_t* code_w = nullptr;
-    // the update rule (vaeb_ae_set_optimizer; {ADAGRAD, c.eta, 0, 0, 1e-6} from create): launch
-    // arguments as the prior above.  acc is slot 0 of its state, acc2 slot 1 (allocated when a
-    // two-slot rule is first set); opt_t counts the optimiser steps taken (Adam's t - 1 of the next)
-    vaeb_ae_optimizer opt{};
-    float* acc2 = nullptr;
-    int64_t opt_t = 0;
 };
 
 namespace {
@@ -113,16 +100,7 @@ int ae_iw_scratch(vaeb_ae* a) {
     return a->mem.lazy(&a->iw_yrow, B);
 }
 
-int ae_reserve(vaeb_ae* a, int n_idx, int n_out) {
-    if (int rc = a->mem.grow(&a->idx, &a->idx_cap, n_idx)) return rc;
-    return a->mem.grow(&a->outs, &a->outs_cap, n_out);
-}
-
 // ------------------------------------------------------------------ forward
-// Rows of a row-major matrix p [rows x width]: row m of a launch is p[m], or p[idx[m]] when
-// idx is set (the dataset rows of a step; the chunk rows the stacked sample planes observe).
-struct AeRows { const float* p; int rows; const int* idx; };
-
 // eps of one latent forward (ae::PAeFwd F_LATENT): zero (the deterministic predictions), or the
 // noise of rows [r0, r0 + ...) of a call in the context's eps mode: rows of the pushed host eps, or
 // Philox at the step counter, for training (domain 0, keyed by the dataset rows `rows`) or
@@ -157,23 +135,9 @@ int ae_corrupt_rows(vaeb_ae* a, const int* idx, int M, int64_t lb) {
     return 0;
 }
 
-// The arguments every forward launch of layer l shares: M rows of in through W and b.
-template <class P>
-P ae_fwd_args(const vaeb_ae* a, const AeLayer& l, const AeRows& in, int M) {
-    P p{};
-    p.M = M; p.N = l.N; p.K = l.K;
-    p.in = in.p; p.ldin = l.K; p.in_rows = in.rows; p.idx = in.idx;
-    p.W = a->theta + l.oW; p.b = a->theta + l.ob;
-    return p;
-}
-
-// out = f(in W + b) (ae::F_ACT) or in W + b (ae::F_LINEAR)
+// out = f(in W + b) (ae::F_ACT) or in W + b (ae::F_LINEAR) under theta
 int ae_fwd_layer(vaeb_ae* a, const AeLayer& l, const AeRows& in, int M, int mode, float* out) {
-    ae::PAeFwd p = ae_fwd_args<ae::PAeFwd>(a, l, in, M);
-    p.mode = mode; p.act = a->c.act; p.out = out;
-    launch_bigk<1>(a->s, p);
-    CHECK_LAUNCH();
-    return 0;
+    return core_fwd_layer(a, a->theta, l, in, M, mode, out);
 }
 
 // Encoder and latent for the M rows of x: H[], then Z, or with a Gaussian latent mu, lv, the -KL
@@ -186,7 +150,7 @@ int ae_encode(vaeb_ae* a, const AeRows& x, int M, const AeNoise& nz) {
     if (!ae_gauss(a))   // Z = H Wz + bz, or f of it (the activated latent)
         return ae_fwd_layer(a, a->lat.l[0], h, M, ae_act_latent(a) ? ae::F_ACT : ae::F_LINEAR, a->Z);
     auto latent = [&](auto p) {   // two-mode prior: kl holds the latent_row partials at z
-        p = ae_fwd_args<decltype(p)>(a, a->lat.l[0], h, M);
+        p = ae_fwd_args<decltype(p)>(a->theta, a->lat.l[0], h, M);
         p.W2 = a->theta + a->lat.l[1].oW; p.b2 = a->theta + a->lat.l[1].ob;
         p.mode = ae::F_LATENT; p.out = a->mu; p.out2 = a->lv; p.zout = a->Z;
         p.llpart = a->kl; p.nct = cdiv(a->c.Dz, 16);
@@ -230,7 +194,7 @@ int ae_output(vaeb_ae* a, int M, AeOut what, const AeRows& y = AeRows{}) {
     const bool obs = what != AE_OUT_PREDICT, deltas = what == AE_OUT_PREDICT || what == AE_OUT_TRAIN;
     const bool se = what == AE_OUT_SQ || (obs && g.otype == VAEB_AE_SE), cont = g.otype == VAEB_AE_CONT;
     auto args = [&](auto p, int mode) {
-        p = ae_fwd_args<decltype(p)>(a, a->out.l[0], AeRows{a->G[g.n_dec], M}, M);
+        p = ae_fwd_args<decltype(p)>(a->theta, a->out.l[0], AeRows{a->G[g.n_dec], M}, M);
         p.out = a->Xpr;
         if (obs) { p.Y = y.p; p.yidx = y.idx; p.ldy = g.Dobs; p.y_rows = y.rows; }
         p.dA = deltas ? a->dA : nullptr; p.llpart = a->ll; p.nct = cdiv(g.Dobs, 16);
@@ -252,99 +216,20 @@ int ae_output(vaeb_ae* a, int M, AeOut what, const AeRows& y = AeRows{}) {
 }
 
 // ------------------------------------------------------------------ backward
-// A rule's own launch arguments into its parameter block (nothing into AdaGrad's: the overload is
-// chosen by the block's base).  Adam's bias corrections are those of the step being enqueued,
-// t = opt_t + 1, formed in double: every step of a vaeb_ae_train_many carries its own.
-bool ae_two_slot(int rule) { return rule == VAEB_AE_RULE_ADADELTA || rule == VAEB_AE_RULE_ADAM; }
-// The optimiser of a layer-stack context as its launches see it: the rule and its numbers, the
-// steps taken and state slot 1 (vaeb_ae and vaeb_clf both hold these three).
-struct AeOptView { const vaeb_ae_optimizer& opt; int64_t opt_t; float* acc2; };
-void ae_put_rule(const AeOptView&, ae::AeRuleArgs<ae::RULE_ADAGRAD>&) {}
-void ae_put_rule(const AeOptView& a, ae::AeRuleArgs<ae::RULE_SGA>& q) { q.mu = a.opt.beta1; }
-void ae_put_rule(const AeOptView& a, ae::AeRuleArgs<ae::RULE_ADADELTA>& q) {
-    q.state1 = a.acc2; q.rho = a.opt.beta1; q.eps = a.opt.eps;
-}
-void ae_put_rule(const AeOptView& a, ae::AeRuleArgs<ae::RULE_ADAM>& q) {
-    const double t = (double)(a.opt_t + 1);
-    q.state1 = a.acc2; q.b1 = a.opt.beta1; q.b2 = a.opt.beta2; q.eps = a.opt.eps;
-    q.bc1 = (float)(1.0 - std::pow((double)a.opt.beta1, t));
-    q.bc2 = (float)(1.0 - std::pow((double)a.opt.beta2, t));
-}
-
-// Why a vaeb_ae_optimizer is not valid, or nullptr (the rules of vaeb_ae_set_optimizer).
-const char* ae_opt_why(const vaeb_ae_optimizer* o) {
-    auto unit = [](float b) { return b >= 0.f && b < 1.f; };   // NaN fails
-    if (!(o->eta > 0.f) || !std::isfinite(o->eta)) return "eta must be finite and > 0";
-    switch (o->rule) {
-    case VAEB_AE_RULE_ADAGRAD:
-        if (o->eps != 1e-6f) return "AdaGrad's eps is 1e-6 (the kernel's literal)";
-        if (o->beta1 != 0.f || o->beta2 != 0.f) return "AdaGrad uses no beta: beta1 and beta2 must be 0";
-        return nullptr;
-    case VAEB_AE_RULE_SGA:
-        if (!unit(o->beta1)) return "the momentum (beta1) must be in [0, 1)";
-        if (o->beta2 != 0.f || o->eps != 0.f) return "gradient ascent uses beta1 alone: beta2 and eps must be 0";
-        return nullptr;
-    case VAEB_AE_RULE_ADADELTA:
-        if (!unit(o->beta1) || o->beta1 == 0.f) return "rho (beta1) must be in (0, 1)";
-        if (!(o->eps > 0.f) || !std::isfinite(o->eps)) return "eps must be finite and > 0";
-        if (o->beta2 != 0.f) return "AdaDelta uses no beta2: it must be 0";
-        return nullptr;
-    case VAEB_AE_RULE_ADAM:
-        if (!unit(o->beta1) || !unit(o->beta2)) return "beta1 and beta2 must be in [0, 1)";
-        if (!(o->eps > 0.f) || !std::isfinite(o->eps)) return "eps must be finite and > 0";
-        return nullptr;
-    }
-    return "rule must be VAEB_AE_RULE_ADAGRAD | _SGA | _ADADELTA | _ADAM";
-}
-
-// One weight-gradient + update launch for layer l from its input in (gathered through in.idx for
-// the first layer) and its output delta over M rows, in the instantiation of the context's rule:
-// the one place that launches the update.
-int ae_wgrad(vaeb_ae* a, const AeLayer& l, const AeRows& in, const float* dout, int M) {
-    auto launch = [&](auto p) {
-        p.M = l.K + 1; p.N = l.N; p.K = M;
-        p.in = in.p; p.ldin = l.K; p.in_rows = in.rows; p.idx = in.idx; p.Kin = l.K;
-        p.dout = dout;
-        p.theta = a->theta; p.accum = a->acc; p.offW = l.oW; p.offb = l.ob;
-        p.eta = a->opt.eta; p.inv_s2 = 1.0f / a->c.s2;
-        ae_put_rule(AeOptView{a->opt, a->opt_t, a->acc2}, p);
-        launch_bigk<1>(a->s, p);
-    };
-    switch (a->opt.rule) {
-    case VAEB_AE_RULE_ADAGRAD: launch(ae::PAeWgrad{}); break;
-    case VAEB_AE_RULE_SGA: launch(ae::PAeWgradT<ae::RULE_SGA>{}); break;
-    case VAEB_AE_RULE_ADADELTA: launch(ae::PAeWgradT<ae::RULE_ADADELTA>{}); break;
-    case VAEB_AE_RULE_ADAM: launch(ae::PAeWgradT<ae::RULE_ADAM>{}); break;
-    default: return fail(VAEB_ERR_STATE, "unknown update rule %d", a->opt.rule);
-    }
-    CHECK_LAUNCH();
-    return 0;
-}
-
 // Backward through one layer of nh (1 or 2) heads l[] with the pre-activation deltas d[] on the
-// input `in` over M rows: the data gradient [d0 | d1] [W0 | W1]^T, then mode, into din with the
-// old weights (din == nullptr: none, no data gradient into x), followed by each head's update.
-// This order is load-bearing (ae_mlp.hpp: every weight is updated only after the last kernel of
-// the step that reads it), and it exists here only.
+// input `in` over M rows (core_bwd_layer: the data gradient, then mode, into din with the old
+// theta; din == nullptr: none; then each head's update with the prior's 1 / s2).  The latent modes
+// read mu, lv and z and leave dmu and dlv; IW: the sample weights; TM: the prior's arguments.
 template <bool IW = false, bool TM = false>
 int ae_bwd_layer(vaeb_ae* a, const AeLayer* l, float* const* d, int nh, const AeRows& in, int M, int mode, float* din) {
-    if (din) {
-        ae::PAeBwdT<IW, TM> p{};
-        p.M = M; p.N = l[0].K; p.K = nh * l[0].N;
-        p.dout = d[0]; p.K1 = l[0].N; p.W = a->theta + l[0].oW;
-        if (nh == 2) { p.dout2 = d[1]; p.W2 = a->theta + l[1].oW; }
-        p.h = in.p; p.mode = mode; p.act = a->c.act; p.din = din;
+    auto fill = [a, mode, M](ae::PAeBwdT<IW, TM>& p) {
         if (mode == ae::B_LATENT || mode == ae::B_LATENT_IW) {
             p.h = a->mu; p.h2 = a->lv; p.h3 = a->Z; p.din = a->dmu; p.din2 = a->dlv;
         }
         if constexpr (IW) { p.wt = a->iw_wt; p.Mp = M / a->c.iw_samples; }
         ae_put_prior(a, p);
-        launch_bigk<1>(a->s, p);
-        CHECK_LAUNCH();
-    }
-    for (int j = 0; j < nh; ++j)
-        if (int rc = ae_wgrad(a, l[j], in, d[j], M)) return rc;
-    return 0;
+    };
+    return core_bwd_layer<ae::PAeBwdT<IW, TM>>(a, a->theta, l, d, nh, in, M, mode, din, 1.0f / a->c.s2, nullptr, fill);
 }
 
 // Output layer and decoder (top down) over R rows; dG[i+1] is the pre-activation delta of layer i.
@@ -464,44 +349,11 @@ int ae_step(vaeb_ae* a, const int* idx, int M, int slot, int64_t lb, int64_t n) 
     return 0;
 }
 
-int ae_check_idx(vaeb_ae* a, const int32_t* idx, int32_t n) {
-    if (!a->data) return fail(VAEB_ERR_STATE, "vaeb_ae_set_data has not been called");
-    for (int i = 0; i < n; ++i)
-        if (idx[i] < 0 || idx[i] >= a->nrows)
-            return fail(VAEB_ERR_ARG, "row index %d out of range [0, %lld)", idx[i], (long long)a->nrows);
-    return 0;
-}
-
 // ------------------------------------------------------------------ calls over host rows
-// Walks the n rows of the host matrix x [n x width] in chunks of at most max_batch rows: uploads
-// a chunk to xin, then body(r0, rows).  The body ends in the chunk's one stream synchronise.
+// The n rows of the host matrix x [n x width] in chunks through xin (core_chunks).
 template <class Body>
 int ae_chunks(vaeb_ae* a, const float* x, int64_t n, int width, Body body) {
-    const int64_t B = a->c.max_batch;
-    for (int64_t r0 = 0; r0 < n; r0 += B) {
-        const int rows = (int)std::min<int64_t>(B, n - r0);
-        HIP_TRY(hipMemcpyAsync(a->xin, x + r0 * width, sizeof(float) * (size_t)rows * width, hipMemcpyHostToDevice,
-                               a->s));
-        if (int rc = body(r0, rows)) return rc;
-    }
-    return 0;
-}
-
-// The fixed-order fp64 sum of the chunk's row values v [rows] -> esum (v == nullptr: a kernel of
-// the body has written esum already), added to *total on the host; the rows themselves to
-// out_rows when that is set.  Ends in the chunk's one stream synchronise.
-int ae_sum_to_host(vaeb_ae* a, const float* v, int rows, double* total, float* out_rows = nullptr) {
-    if (v) {
-        HIP_TRY(hipMemsetAsync(a->esum, 0, sizeof(double), a->s));
-        hipLaunchKernelGGL(iw_sum_kernel, dim3(1), dim3(256), 0, a->s, v, (int64_t)rows, a->esum);
-        CHECK_LAUNCH();
-    }
-    double part = 0.0;
-    HIP_TRY(hipMemcpyAsync(&part, a->esum, sizeof(double), hipMemcpyDeviceToHost, a->s));
-    if (out_rows) HIP_TRY(hipMemcpyAsync(out_rows, v, sizeof(float) * (size_t)rows, hipMemcpyDeviceToHost, a->s));
-    HIP_TRY(hipStreamSynchronize(a->s));
-    *total += part;
-    return 0;
+    return core_chunks(a, n, x, width, a->xin, nullptr, 0, nullptr, body);
 }
 
 enum AePredict { AE_RECONSTRUCT, AE_ENCODE, AE_DECODE };
@@ -524,64 +376,6 @@ int ae_predict(vaeb_ae* a, const float* x, int64_t n, float* out, AePredict what
         HIP_TRY(hipStreamSynchronize(a->s));
         return 0;
     });
-}
-
-// The optimiser state and arena transfers of a layer-stack context, shared by vaeb_ae and vaeb_clf:
-// both hold P, s, mem, acc, acc2, opt and opt_t under these names.
-template <class Ctx>
-int ae_xfer(Ctx* a, float* dev, const float* hin, float* hout, int64_t n) {
-    if (!a || (!hin && !hout)) return fail(VAEB_ERR_ARG, "null argument");
-    if (n != a->P) return fail(VAEB_ERR_ARG, "size mismatch: got %lld, expected %lld", (long long)n, (long long)a->P);
-    HIP_TRY(hipStreamSynchronize(a->s));
-    if (hin) HIP_TRY(hipMemcpy(dev, hin, sizeof(float) * n, hipMemcpyHostToDevice));
-    else HIP_TRY(hipMemcpy(hout, dev, sizeof(float) * n, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-// vaeb_ae_set_optimizer's body.  The fields a rule does not use are 0 (AdaGrad's eps: the kernel's
-// literal 1e-6).
-template <class Ctx>
-int ae_set_optimizer(Ctx* a, const vaeb_ae_optimizer* o) {
-    if (!a || !o) return fail(VAEB_ERR_ARG, "null argument");
-    const char* why = ae_opt_why(o);
-    if (why)
-        return fail(VAEB_ERR_ARG, "optimizer {rule %d, eta %g, beta1 %g, beta2 %g, eps %g}: %s", o->rule, (double)o->eta,
-                    (double)o->beta1, (double)o->beta2, (double)o->eps, why);
-    if (o->rule != a->opt.rule) {   // another rule: its state starts from zero, after the enqueued steps
-        if (ae_two_slot(o->rule))
-            if (int rc = a->mem.lazy(&a->acc2, a->P)) return rc;
-        HIP_TRY(hipMemsetAsync(a->acc, 0, sizeof(float) * (size_t)a->P, a->s));
-        if (a->acc2) HIP_TRY(hipMemsetAsync(a->acc2, 0, sizeof(float) * (size_t)a->P, a->s));
-        a->opt_t = 0;
-    }
-    a->opt = *o;   // launch arguments: the enqueued steps keep theirs
-    return 0;
-}
-
-template <class Ctx>
-float* ae_opt_slot(Ctx* a, int32_t slot) {
-    if (!a) return nullptr;
-    if (slot == 0) return a->acc;
-    if (slot == 1 && ae_two_slot(a->opt.rule)) return a->acc2;
-    fail(VAEB_ERR_ARG, "optimizer state slot %d: rule %d has slot 0%s", slot, a->opt.rule,
-         ae_two_slot(a->opt.rule) ? " and slot 1" : " only");
-    return nullptr;
-}
-
-// set / get of state slot `slot` (hin or hout set)
-template <class Ctx>
-int ae_opt_state(Ctx* a, int32_t slot, const float* hin, float* hout, int64_t n) {
-    if (!a || (!hin && !hout)) return fail(VAEB_ERR_ARG, "null argument");
-    float* dev = ae_opt_slot(a, slot);
-    return dev ? ae_xfer(a, dev, hin, hout, n) : VAEB_ERR_ARG;
-}
-
-template <class Ctx>
-int ae_set_opt_step(Ctx* a, int64_t t) {
-    if (!a) return fail(VAEB_ERR_ARG, "null argument");
-    if (t < 0) return fail(VAEB_ERR_ARG, "optimizer step %lld < 0", (long long)t);
-    a->opt_t = t;
-    return 0;
 }
 
 }  // namespace
@@ -621,11 +415,6 @@ int vaeb_ae_create(const vaeb_ae_config* cfg, vaeb_ae** out) {
         return fail(VAEB_ERR_ARG, "corruption needs max_batch * Dobs < 2^29 (the corrupted rows' 32-bit byte offsets)");
     auto* a = new vaeb_ae();
     a->c = g;
-    a->opt = vaeb_ae_optimizer{VAEB_AE_RULE_ADAGRAD, g.eta, 0.f, 0.f, 1e-6f};
-    if (hipSetDevice(g.device) != hipSuccess || hipStreamCreateWithFlags(&a->s, hipStreamNonBlocking) != hipSuccess) {
-        delete a;
-        return fail(VAEB_ERR_HIP, "device / stream init failed");
-    }
     for (int i = 0; i < g.n_enc; ++i) { a->enc[i].K = i ? g.Denc[i - 1] : g.Dobs; a->enc[i].N = g.Denc[i]; }
     for (int i = 0; i < g.n_dec; ++i) { a->dec[i].K = i ? g.Ddec[i - 1] : g.Dz; a->dec[i].N = g.Ddec[i]; }
     a->lat.n = ae_gauss(a) ? 2 : 1;              // Wz, or as the cont output: Wzmu, Wzlv
@@ -635,20 +424,13 @@ int vaeb_ae_create(const vaeb_ae_config* cfg, vaeb_ae** out) {
         a->out.l[j].K = g.Ddec[g.n_dec - 1]; a->out.l[j].N = g.Dobs;
     }
     // theta order (ae.py:51,56,64,72): encoder, latent, decoder, output; each group's W's, then its b's
-    int64_t o = 0;
-    auto place = [&o](AeLayer* l, int n) {
-        for (int i = 0; i < n; ++i) { l[i].oW = o; o += (int64_t)l[i].K * l[i].N; }
-        for (int i = 0; i < n; ++i) { l[i].ob = o; o += l[i].N; }
-    };
-    place(a->enc, g.n_enc);
-    place(a->lat.l, a->lat.n);
-    place(a->dec, g.n_dec);
-    place(a->out.l, a->out.n);
-    a->P = o;
+    core_place(&a->P, a->enc, g.n_enc);
+    core_place(&a->P, a->lat.l, a->lat.n);
+    core_place(&a->P, a->dec, g.n_dec);
+    core_place(&a->P, a->out.l, a->out.n);
+    int rc = core_open(a, g.device, g.eta, g.act, g.max_batch);
+    if (rc) { delete a; return rc; }
     const int64_t B = g.max_batch;
-    int rc = 0;
-    rc = rc ? rc : a->mem.alloc(&a->theta, a->P);
-    rc = rc ? rc : a->mem.alloc(&a->acc, a->P);
     for (int i = 1; i <= g.n_enc; ++i) {
         rc = rc ? rc : a->mem.alloc(&a->H[i], B * a->enc[i - 1].N);
         rc = rc ? rc : a->mem.alloc(&a->dH[i], B * a->enc[i - 1].N);
@@ -674,29 +456,20 @@ int vaeb_ae_create(const vaeb_ae_config* cfg, vaeb_ae** out) {
         rc = rc ? rc : a->mem.alloc(&a->iw_lw, B);
     }
     if (ae_corrupting(a)) rc = rc ? rc : a->mem.alloc(&a->xc, B * g.Dobs);
-    rc = rc ? rc : ae_reserve(a, (int)B, 1);
     a->out.d[0] = a->dA; a->out.d[1] = a->dA2;
     a->lat.d[0] = ae_gauss(a) ? a->dmu : a->dZ; a->lat.d[1] = a->dlv;
-    if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(VAEB_ERR_HIP, "device init failed");
-    if (rc) { vaeb_ae_destroy(a); return rc; }
+    if ((rc = core_ready(a, rc))) { delete a; return rc; }
     *out = a;
     return 0;
 }
 
 int vaeb_ae_destroy(vaeb_ae* a) {
-    if (!a) return 0;
-    if (a->s) hipStreamSynchronize(a->s);
-    a->mem.release_all();
-    if (a->s) hipStreamDestroy(a->s);
+    if (a) core_close(a);
     delete a;
     return 0;
 }
 
-int vaeb_ae_num_params(const vaeb_ae* a, int64_t* n) {
-    if (!a || !n) return fail(VAEB_ERR_ARG, "null argument");
-    *n = a->P;
-    return 0;
-}
+int vaeb_ae_num_params(const vaeb_ae* a, int64_t* n) { return core_num_params(a, n); }
 
 int vaeb_ae_set_data(vaeb_ae* a, const float* x, int64_t n_rows) {
     if (!a || !x || n_rows <= 0) return fail(VAEB_ERR_ARG, "bad data arguments");
@@ -707,51 +480,34 @@ int vaeb_ae_set_data(vaeb_ae* a, const float* x, int64_t n_rows) {
     return 0;
 }
 
-int vaeb_ae_set_params(vaeb_ae* a, const float* f, int64_t n) { return ae_xfer(a, a ? a->theta : nullptr, f, nullptr, n); }
-int vaeb_ae_get_params(vaeb_ae* a, float* f, int64_t n) { return ae_xfer(a, a ? a->theta : nullptr, nullptr, f, n); }
-int vaeb_ae_set_adagrad_state(vaeb_ae* a, const float* f, int64_t n) { return ae_xfer(a, a ? a->acc : nullptr, f, nullptr, n); }
-int vaeb_ae_get_adagrad_state(vaeb_ae* a, float* f, int64_t n) { return ae_xfer(a, a ? a->acc : nullptr, nullptr, f, n); }
+int vaeb_ae_set_params(vaeb_ae* a, const float* f, int64_t n) { return core_xfer(a, a ? a->theta : nullptr, f, nullptr, n); }
+int vaeb_ae_get_params(vaeb_ae* a, float* f, int64_t n) { return core_xfer(a, a ? a->theta : nullptr, nullptr, f, n); }
+int vaeb_ae_set_adagrad_state(vaeb_ae* a, const float* f, int64_t n) { return core_xfer(a, a ? a->acc : nullptr, f, nullptr, n); }
+int vaeb_ae_get_adagrad_state(vaeb_ae* a, float* f, int64_t n) { return core_xfer(a, a ? a->acc : nullptr, nullptr, f, n); }
 
 // ------------------------------------------------------------------ the update rule
-int vaeb_ae_set_optimizer(vaeb_ae* a, const vaeb_ae_optimizer* o) { return ae_set_optimizer(a, o); }
+int vaeb_ae_set_optimizer(vaeb_ae* a, const vaeb_ae_optimizer* o) { return core_set_optimizer(a, o); }
+int vaeb_ae_get_optimizer(vaeb_ae* a, vaeb_ae_optimizer* o) { return core_get_optimizer(a, o); }
+int vaeb_ae_set_opt_state(vaeb_ae* a, int32_t slot, const float* f, int64_t n) { return core_opt_state(a, slot, f, nullptr, n); }
+int vaeb_ae_get_opt_state(vaeb_ae* a, int32_t slot, float* f, int64_t n) { return core_opt_state(a, slot, nullptr, f, n); }
+int vaeb_ae_set_opt_step(vaeb_ae* a, int64_t t) { return core_set_opt_step(a, t); }
+int vaeb_ae_get_opt_step(vaeb_ae* a, int64_t* t) { return core_get_opt_step(a, t); }
 
-int vaeb_ae_get_optimizer(vaeb_ae* a, vaeb_ae_optimizer* o) {
-    if (!a || !o) return fail(VAEB_ERR_ARG, "null argument");
-    *o = a->opt;
-    return 0;
-}
-
-int vaeb_ae_set_opt_state(vaeb_ae* a, int32_t slot, const float* f, int64_t n) { return ae_opt_state(a, slot, f, nullptr, n); }
-int vaeb_ae_get_opt_state(vaeb_ae* a, int32_t slot, float* f, int64_t n) { return ae_opt_state(a, slot, nullptr, f, n); }
-int vaeb_ae_set_opt_step(vaeb_ae* a, int64_t t) { return ae_set_opt_step(a, t); }
-
-int vaeb_ae_get_opt_step(vaeb_ae* a, int64_t* t) {
-    if (!a || !t) return fail(VAEB_ERR_ARG, "null argument");
-    *t = a->opt_t;
-    return 0;
-}
-
+// The shared checks (core_train_many), then this handle's: the stacked sample planes against
+// max_batch, the pushed host eps and corruption noise.
 int vaeb_ae_train_many(vaeb_ae* a, const int32_t* idx, int32_t n, int32_t batch, float* out) {
-    if (!a || !idx || !out || n <= 0 || batch <= 0) return fail(VAEB_ERR_ARG, "bad arguments");
-    if (batch > a->c.max_batch) return fail(VAEB_ERR_ARG, "batch %d > max_batch %d", batch, a->c.max_batch);
-    if (int rc = ae_check_idx(a, idx, n)) return rc;
-    const bool iw = ae_iw(a);
-    if (iw && (int64_t)a->c.iw_samples * std::min(batch, n) > a->c.max_batch)
-        return fail(VAEB_ERR_ARG, "iw_samples %d x batch %d > max_batch %d (the stacked sample planes)",
-                    a->c.iw_samples, std::min(batch, n), a->c.max_batch);
-    if (ae_gauss(a))
-        if (int rc = ae_host_eps_ready(a, iw ? (int64_t)a->c.iw_samples * n : (int64_t)n)) return rc;
-    if (int rc = ae_host_corruption_ready(a, n)) return rc;
-    const int nb = cdiv(n, batch);
-    if (int rc = ae_reserve(a, n, nb)) return rc;
-    HIP_TRY(hipMemcpyAsync(a->idx, idx, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, a->s));
-    for (int j = 0; j < nb; ++j) {
-        const int lb = j * batch, m = std::min(batch, n - lb);
-        if (int rc = ae_step(a, a->idx + lb, m, j, lb, n)) return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(out, a->outs, sizeof(float) * (size_t)nb, hipMemcpyDeviceToHost, a->s));
-    HIP_TRY(hipStreamSynchronize(a->s));
-    return 0;
+    if (!a) return fail(VAEB_ERR_ARG, "bad arguments");
+    auto more = [&]() -> int {
+        const bool iw = ae_iw(a);
+        if (iw && (int64_t)a->c.iw_samples * std::min(batch, n) > a->c.max_batch)
+            return fail(VAEB_ERR_ARG, "iw_samples %d x batch %d > max_batch %d (the stacked sample planes)",
+                        a->c.iw_samples, std::min(batch, n), a->c.max_batch);
+        if (ae_gauss(a))
+            if (int rc = ae_host_eps_ready(a, iw ? (int64_t)a->c.iw_samples * n : (int64_t)n)) return rc;
+        return ae_host_corruption_ready(a, n);
+    };
+    auto step = [a](const int* rows, int m, int slot, int64_t lb, int64_t nn) { return ae_step(a, rows, m, slot, lb, nn); };
+    return core_train_many(a, a->data, a->nrows, "vaeb_ae_set_data", idx, n, batch, out, more, step);
 }
 
 int vaeb_ae_train(vaeb_ae* a, const int32_t* idx, int32_t n, float* out) {
@@ -778,7 +534,7 @@ int vaeb_ae_sq_error(vaeb_ae* a, const float* x, int64_t n, double* out_sum, flo
             hipLaunchKernelGGL(ae::ae_row_sum_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, a->s, a->ll, rows,
                                cdiv(g.Dobs, 16), a->sq_rows);
             CHECK_LAUNCH();
-            return ae_sum_to_host(a, a->sq_rows, rows, &total, out_rows ? out_rows + r0 : nullptr);
+            return core_sum_to_host(a, a->sq_rows, rows, &total, out_rows ? out_rows + r0 : nullptr);
         })) return rc;
     *out_sum = total;
     return 0;
@@ -871,7 +627,7 @@ int vaeb_ae_elbo(vaeb_ae* a, const float* x, int64_t n, double* out_sum) {
             hipLaunchKernelGGL(ae::ae_elbo_kernel, dim3(1), dim3(256), 0, a->s, a->ll, (int64_t)rows * cdiv(g.Dobs, 16),
                                a->kl, (int64_t)rows * cdiv(g.Dz, 16), rows, (float*)nullptr, 0, a->esum);
             CHECK_LAUNCH();
-            return ae_sum_to_host(a, nullptr, 0, &total);
+            return core_sum_to_host(a, nullptr, 0, &total);
         })) return rc;
     *out_sum = total;
     return 0;
@@ -909,7 +665,7 @@ int vaeb_ae_marginal_ll(vaeb_ae* a, const float* x, int64_t n, int32_t K, double
                 hipLaunchKernelGGL(iw_lse_kernel, dim3(cdiv(R, 256)), dim3(256), 0, a->s, w);
                 CHECK_LAUNCH();
             }
-            return ae_sum_to_host(a, w.rows, R, &total, out_rows ? out_rows + r0 : nullptr);
+            return core_sum_to_host(a, w.rows, R, &total, out_rows ? out_rows + r0 : nullptr);
         })) return rc;
     *out_sum = total;
     return 0;
@@ -1019,9 +775,9 @@ int vaeb_ae_push_corruption(vaeb_ae* a, const float* r, int64_t rows) {
 int vaeb_ae_corrupt(vaeb_ae* a, const int32_t* idx, int32_t n, float* out) {
     AE_NEED_CORRUPT(a, "vaeb_ae_corrupt");
     if (!idx || !out || n <= 0) return fail(VAEB_ERR_ARG, "bad arguments");
-    if (int rc = ae_check_idx(a, idx, n)) return rc;
+    if (int rc = core_check_idx(a->data, a->nrows, "vaeb_ae_set_data", idx, n)) return rc;
     if (int rc = ae_host_corruption_ready(a, n)) return rc;
-    if (int rc = ae_reserve(a, n, 1)) return rc;
+    if (int rc = core_reserve(a, n, 1)) return rc;
     const int D = a->c.Dobs;
     HIP_TRY(hipMemcpyAsync(a->idx, idx, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, a->s));
     for (int64_t lb = 0; lb < n; lb += a->c.max_batch) {

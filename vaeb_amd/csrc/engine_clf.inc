@@ -1,44 +1,33 @@
 // engine_clf.inc -- the softmax MLP classifier (include/vaeb_hip.h vaeb_clf_*) on the layer-stack
-// kernels (ae_mlp.hpp) and clf_softmax.hpp.  Included by vaeb_hip.hip after engine_ae.inc, whose
-// AeLayer, AeRows, AeOptView / ae_put_rule and the optimiser / arena calls' bodies (ae_set_optimizer,
-// ae_opt_state, ae_set_opt_step, ae_xfer) it shares.  Each call and
-// the helper sequence it runs:
-//   vaeb_clf_train(_many)  per batch clf_step: (dropout: clf_mask, training domain) | clf_forward |
-//                          clf_softmax (value + P + deltas) | ae_loglik_kernel (the sum) | per layer,
-//                          top down, clf_bwd_layer: the data gradient with the old weights, then
-//                          that layer's weight gradient + update
+// kernels (ae_mlp.hpp) and clf_softmax.hpp.  Included by vaeb_hip.hip after stack_core.inc: vaeb_clf
+// is a StackCore, as vaeb_ae is, and every launch of the layer-stack kernels, the update rule's
+// calls, the training driver, the chunk loop and the chunk sum are the core's.  Each call and the
+// helper sequence it runs:
+//   vaeb_clf_train(_many)  core_train_many, per batch clf_step: (dropout: clf_mask, training domain) |
+//                          clf_forward (core_fwd_layer per layer) | clf_softmax (value + P + deltas) |
+//                          ae_loglik_kernel (the sum) | per layer, top down, clf_bwd_layer =
+//                          core_bwd_layer, one head, B_DACT
 //   vaeb_clf_predict       clf_chunks: clf_probs = per draw (clf_mask, evaluation domain) |
 //                          clf_forward | clf_softmax (predictions; draws >= 1: the running mean)
-//   vaeb_clf_loglik        clf_chunks: clf_forward | clf_softmax (value) | iw_sum_kernel
+//   vaeb_clf_loglik        clf_chunks: clf_forward | clf_softmax (value) | core_sum_to_host
 //   vaeb_clf_accuracy      clf_chunks: clf_probs | clf_hit_kernel | clf_count_kernel
 //   vaeb_clf_draw_mask     clf_mask (mask bytes only)
 // A dropout context's forward and data-backward launches read the masked arena thm where a MAP
 // context's read theta: a pointer, no other kernel.  Its weight-gradient launch is the MASK
-// instantiation PAeWgradT<RULE, true>, which updates the real theta.
+// instantiation PAeWgradT<RULE, true> (core_wgrad given the mask), which updates the real theta.
 
-struct vaeb_clf {
+struct vaeb_clf : StackCore {
     vaeb_clf_config c{};
-    hipStream_t s = nullptr;
-    int64_t P = 0;
     AeLayer hid[VAEB_AE_MAX_LAYERS] = {}, out{};   // Din -> Dh..., then Dh[n - 1] -> Dout
-    DevOwner mem;                                  // every device allocation; released by vaeb_clf_destroy
-    float *theta = nullptr, *acc = nullptr, *acc2 = nullptr;
     float* thm = nullptr;                          // dropout: theta * m of the last draw
     uint8_t* mask = nullptr;                       // dropout: m of the last draw [P]
     float *x = nullptr, *y = nullptr;              // resident Xtr, Ytr
     int64_t nrows = 0;
-    int* idx = nullptr;
-    int64_t idx_cap = 0;
-    float* outs = nullptr;
-    int64_t outs_cap = 0;
     float *H[VAEB_AE_MAX_LAYERS + 1] = {}, *dH[VAEB_AE_MAX_LAYERS + 1] = {};   // H[0], dH[0] unused
     float *A = nullptr, *Pr = nullptr, *dA = nullptr, *rowval = nullptr;       // logits, P, deltas, row values
     float *Pacc = nullptr, *xin = nullptr, *yin = nullptr;                     // MC mean; a chunk's host rows
     int* hit = nullptr;
     long long* count = nullptr;
-    double* esum = nullptr;
-    vaeb_ae_optimizer opt{};
-    int64_t opt_t = 0;
     uint64_t seed = 0;
     int64_t step = 0;                              // Philox step counter of the dropout draws
     uint64_t T = 0;                                // keep iff word < T: floor(keep * 2^32)
@@ -69,19 +58,10 @@ int clf_eval_weights(vaeb_clf* c, int draw, const float** th) {
 // Hidden activations H[1..n] and the logits A of the M rows of x under the arena th.
 int clf_forward(vaeb_clf* c, const float* th, const AeRows& x, int M) {
     const int nh = c->c.n_hidden;
-    for (int i = 0; i <= nh; ++i) {
-        const AeLayer& l = i < nh ? c->hid[i] : c->out;
-        const AeRows in = i == 0 ? x : AeRows{c->H[i], M, nullptr};
-        ae::PAeFwd p{};
-        p.M = M; p.N = l.N; p.K = l.K;
-        p.in = in.p; p.ldin = l.K; p.in_rows = in.rows; p.idx = in.idx;
-        p.W = th + l.oW; p.b = th + l.ob;
-        p.mode = i < nh ? ae::F_ACT : ae::F_LINEAR; p.act = c->c.act;
-        p.out = i < nh ? c->H[i + 1] : c->A;
-        launch_bigk<1>(c->s, p);
-        CHECK_LAUNCH();
-    }
-    return 0;
+    for (int i = 0; i < nh; ++i)
+        if (int rc = core_fwd_layer(c, th, c->hid[i], i == 0 ? x : AeRows{c->H[i], M, nullptr}, M, ae::F_ACT, c->H[i + 1]))
+            return rc;
+    return core_fwd_layer(c, th, c->out, AeRows{c->H[nh], M, nullptr}, M, ae::F_LINEAR, c->A);
 }
 
 // The softmax output on the logits of M rows.  y.p == nullptr: predictions only.
@@ -96,52 +76,13 @@ int clf_softmax(vaeb_clf* c, int M, const AeRows& y, float* P, float* d, float* 
     return 0;
 }
 
-// One weight-gradient + update launch for layer l (ae_wgrad's arguments; inv_s2 = 0 without a
-// prior), in the MASK instantiation on a dropout context.
-int clf_wgrad(vaeb_clf* c, const AeLayer& l, const AeRows& in, const float* dout, int M) {
-    auto launch = [&](auto p) {
-        p.M = l.K + 1; p.N = l.N; p.K = M;
-        p.in = in.p; p.ldin = l.K; p.in_rows = in.rows; p.idx = in.idx; p.Kin = l.K;
-        p.dout = dout;
-        p.theta = c->theta; p.accum = c->acc; p.offW = l.oW; p.offb = l.ob;
-        p.eta = c->opt.eta; p.inv_s2 = c->c.prior ? 1.0f / c->c.s2 : 0.f;
-        ae_put_rule(AeOptView{c->opt, c->opt_t, c->acc2}, p);
-        if constexpr (std::is_base_of_v<ae::AeMaskArgs<true>, decltype(p)>) p.mask = c->mask;
-        launch_bigk<1>(c->s, p);
-    };
-    const bool dr = clf_dropout(c);
-    switch (c->opt.rule) {
-    case VAEB_AE_RULE_ADAGRAD:
-        if (dr) launch(ae::PAeWgradT<ae::RULE_ADAGRAD, true>{}); else launch(ae::PAeWgrad{});
-        break;
-    case VAEB_AE_RULE_SGA:
-        if (dr) launch(ae::PAeWgradT<ae::RULE_SGA, true>{}); else launch(ae::PAeWgradT<ae::RULE_SGA>{});
-        break;
-    case VAEB_AE_RULE_ADADELTA:
-        if (dr) launch(ae::PAeWgradT<ae::RULE_ADADELTA, true>{}); else launch(ae::PAeWgradT<ae::RULE_ADADELTA>{});
-        break;
-    case VAEB_AE_RULE_ADAM:
-        if (dr) launch(ae::PAeWgradT<ae::RULE_ADAM, true>{}); else launch(ae::PAeWgradT<ae::RULE_ADAM>{});
-        break;
-    default: return fail(VAEB_ERR_STATE, "unknown update rule %d", c->opt.rule);
-    }
-    CHECK_LAUNCH();
-    return 0;
-}
-
-// Backward through layer l with the pre-activation delta d of its output over M rows: the data
-// gradient (d W^T) * f'(in) under the arena th into din with the OLD weights (din == nullptr: the
-// first layer, none), then the layer's update -- the order of ae_bwd_layer.
-int clf_bwd_layer(vaeb_clf* c, const float* th, const AeLayer& l, const float* d, const AeRows& in, int M, float* din) {
-    if (din) {
-        ae::PAeBwd p{};
-        p.M = M; p.N = l.K; p.K = l.N;
-        p.dout = d; p.K1 = l.N; p.W = th + l.oW;
-        p.h = in.p; p.mode = ae::B_DACT; p.act = c->c.act; p.din = din;
-        launch_bigk<1>(c->s, p);
-        CHECK_LAUNCH();
-    }
-    return clf_wgrad(c, l, in, d, M);
+// Backward through layer l with the pre-activation delta d of its output over M rows, the
+// one-head B_DACT case of core_bwd_layer: the data gradient (d W^T) * f'(in) under the arena th
+// into din (nullptr: the first layer, none), then the layer's update with the prior's 1 / s2 (0
+// without a prior), masked on a dropout context.
+int clf_bwd_layer(vaeb_clf* c, const float* th, const AeLayer& l, float* d, const AeRows& in, int M, float* din) {
+    return core_bwd_layer<ae::PAeBwd>(c, th, &l, &d, 1, in, M, ae::B_DACT, din, c->c.prior ? 1.0f / c->c.s2 : 0.f, c->mask,
+                                      [](ae::PAeBwd&) {});
 }
 
 // One step on the M resident rows idx (a device list): the log-likelihood sum -> outs[slot].
@@ -166,20 +107,10 @@ int clf_step(vaeb_clf* c, const int* idx, int M, int slot) {
     return 0;
 }
 
-// Walks n host rows of x [n x Din] (and y [n x Dout] when set) in chunks of at most max_batch rows:
-// uploads a chunk to xin (yin), then body(r0, rows).
+// The n host rows of x [n x Din] (and of y [n x Dout] when set) in chunks through xin (yin).
 template <class Body>
 int clf_chunks(vaeb_clf* c, const float* x, const float* y, int64_t n, Body body) {
-    const int64_t B = c->c.max_batch;
-    const int Din = c->c.Din, Dout = c->c.Dout;
-    for (int64_t r0 = 0; r0 < n; r0 += B) {
-        const int rows = (int)std::min<int64_t>(B, n - r0);
-        HIP_TRY(hipMemcpyAsync(c->xin, x + r0 * Din, sizeof(float) * (size_t)rows * Din, hipMemcpyHostToDevice, c->s));
-        if (y)
-            HIP_TRY(hipMemcpyAsync(c->yin, y + r0 * Dout, sizeof(float) * (size_t)rows * Dout, hipMemcpyHostToDevice, c->s));
-        if (int rc = body(r0, rows)) return rc;
-    }
-    return 0;
+    return core_chunks(c, n, x, c->c.Din, c->xin, y, c->c.Dout, c->yin, body);
 }
 
 // P of the chunk in xin: theta as it is (draws == 0, into Pr) or the mean over the evaluation
@@ -231,29 +162,20 @@ int vaeb_clf_create(const vaeb_clf_config* cfg, vaeb_clf** out) {
         return fail(VAEB_ERR_ARG, "dropout needs keep in (0, 1] (got %g)", (double)g.keep);
     auto* c = new vaeb_clf();
     c->c = g;
-    c->opt = vaeb_ae_optimizer{VAEB_AE_RULE_ADAGRAD, g.eta, 0.f, 0.f, 1e-6f};
     c->T = g.dropout ? (uint64_t)std::floor((double)g.keep * 4294967296.0) : 0;
     for (int i = 0; i < g.n_hidden; ++i) { c->hid[i].K = i ? g.Dh[i - 1] : g.Din; c->hid[i].N = g.Dh[i]; }
     c->out.K = g.Dh[g.n_hidden - 1]; c->out.N = g.Dout;
     // theta order (mlp.py:113): the hidden W's, the hidden b's, Wout, bout
-    int64_t o = 0;
-    for (int i = 0; i < g.n_hidden; ++i) { c->hid[i].oW = o; o += (int64_t)c->hid[i].K * c->hid[i].N; }
-    for (int i = 0; i < g.n_hidden; ++i) { c->hid[i].ob = o; o += c->hid[i].N; }
-    c->out.oW = o; o += (int64_t)c->out.K * c->out.N;
-    c->out.ob = o; o += c->out.N;
-    c->P = o;
+    core_place(&c->P, c->hid, g.n_hidden);
+    core_place(&c->P, &c->out, 1);
     if (c->P >= (1ll << 31)) {   // the tile kernels' 32-bit byte offsets need less anyway
+        const long long P = c->P;
         delete c;
-        return fail(VAEB_ERR_ARG, "%lld parameters: the arena holds fewer than 2^31", (long long)o);
+        return fail(VAEB_ERR_ARG, "%lld parameters: the arena holds fewer than 2^31", P);
     }
-    if (hipSetDevice(g.device) != hipSuccess || hipStreamCreateWithFlags(&c->s, hipStreamNonBlocking) != hipSuccess) {
-        delete c;
-        return fail(VAEB_ERR_HIP, "device / stream init failed");
-    }
+    int rc = core_open(c, g.device, g.eta, g.act, g.max_batch);
+    if (rc) { delete c; return rc; }
     const int64_t B = g.max_batch;
-    int rc = 0;
-    rc = rc ? rc : c->mem.alloc(&c->theta, c->P);
-    rc = rc ? rc : c->mem.alloc(&c->acc, c->P);
     if (g.dropout) {
         rc = rc ? rc : c->mem.alloc(&c->thm, c->P);
         rc = rc ? rc : c->mem.alloc(&c->mask, c->P);
@@ -269,28 +191,18 @@ int vaeb_clf_create(const vaeb_clf_config* cfg, vaeb_clf** out) {
     rc = rc ? rc : c->mem.alloc(&c->hit, B);
     rc = rc ? rc : c->mem.alloc(&c->count, 1);
     rc = rc ? rc : c->mem.alloc(&c->esum, 1);
-    rc = rc ? rc : c->mem.grow(&c->idx, &c->idx_cap, B);
-    rc = rc ? rc : c->mem.grow(&c->outs, &c->outs_cap, 1);
-    if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(VAEB_ERR_HIP, "device init failed");
-    if (rc) { vaeb_clf_destroy(c); return rc; }
+    if ((rc = core_ready(c, rc))) { delete c; return rc; }
     *out = c;
     return 0;
 }
 
 int vaeb_clf_destroy(vaeb_clf* c) {
-    if (!c) return 0;
-    if (c->s) hipStreamSynchronize(c->s);
-    c->mem.release_all();
-    if (c->s) hipStreamDestroy(c->s);
+    if (c) core_close(c);
     delete c;
     return 0;
 }
 
-int vaeb_clf_num_params(const vaeb_clf* c, int64_t* n) {
-    if (!c || !n) return fail(VAEB_ERR_ARG, "null argument");
-    *n = c->P;
-    return 0;
-}
+int vaeb_clf_num_params(const vaeb_clf* c, int64_t* n) { return core_num_params(c, n); }
 
 int vaeb_clf_set_data(vaeb_clf* c, const float* x, const float* y, int64_t n_rows) {
     if (!c || !x || !y || n_rows <= 0 || n_rows >= (1ll << 31)) return fail(VAEB_ERR_ARG, "bad data arguments");
@@ -303,27 +215,16 @@ int vaeb_clf_set_data(vaeb_clf* c, const float* x, const float* y, int64_t n_row
     return 0;
 }
 
-int vaeb_clf_set_params(vaeb_clf* c, const float* f, int64_t n) { return ae_xfer(c, c ? c->theta : nullptr, f, nullptr, n); }
-int vaeb_clf_get_params(vaeb_clf* c, float* f, int64_t n) { return ae_xfer(c, c ? c->theta : nullptr, nullptr, f, n); }
+int vaeb_clf_set_params(vaeb_clf* c, const float* f, int64_t n) { return core_xfer(c, c ? c->theta : nullptr, f, nullptr, n); }
+int vaeb_clf_get_params(vaeb_clf* c, float* f, int64_t n) { return core_xfer(c, c ? c->theta : nullptr, nullptr, f, n); }
 
-// The update rule and its state: engine_ae.inc's bodies, shared with vaeb_ae.
-int vaeb_clf_set_optimizer(vaeb_clf* c, const vaeb_ae_optimizer* o) { return ae_set_optimizer(c, o); }
-
-int vaeb_clf_get_optimizer(vaeb_clf* c, vaeb_ae_optimizer* o) {
-    if (!c || !o) return fail(VAEB_ERR_ARG, "null argument");
-    *o = c->opt;
-    return 0;
-}
-
-int vaeb_clf_set_opt_state(vaeb_clf* c, int32_t slot, const float* f, int64_t n) { return ae_opt_state(c, slot, f, nullptr, n); }
-int vaeb_clf_get_opt_state(vaeb_clf* c, int32_t slot, float* f, int64_t n) { return ae_opt_state(c, slot, nullptr, f, n); }
-int vaeb_clf_set_opt_step(vaeb_clf* c, int64_t t) { return ae_set_opt_step(c, t); }
-
-int vaeb_clf_get_opt_step(vaeb_clf* c, int64_t* t) {
-    if (!c || !t) return fail(VAEB_ERR_ARG, "null argument");
-    *t = c->opt_t;
-    return 0;
-}
+// The update rule and its state: the core's bodies, as vaeb_ae's.
+int vaeb_clf_set_optimizer(vaeb_clf* c, const vaeb_ae_optimizer* o) { return core_set_optimizer(c, o); }
+int vaeb_clf_get_optimizer(vaeb_clf* c, vaeb_ae_optimizer* o) { return core_get_optimizer(c, o); }
+int vaeb_clf_set_opt_state(vaeb_clf* c, int32_t slot, const float* f, int64_t n) { return core_opt_state(c, slot, f, nullptr, n); }
+int vaeb_clf_get_opt_state(vaeb_clf* c, int32_t slot, float* f, int64_t n) { return core_opt_state(c, slot, nullptr, f, n); }
+int vaeb_clf_set_opt_step(vaeb_clf* c, int64_t t) { return core_set_opt_step(c, t); }
+int vaeb_clf_get_opt_step(vaeb_clf* c, int64_t* t) { return core_get_opt_step(c, t); }
 
 int vaeb_clf_set_seed(vaeb_clf* c, uint64_t seed) {
     if (!c) return fail(VAEB_ERR_ARG, "null argument");
@@ -345,23 +246,9 @@ int vaeb_clf_get_step(vaeb_clf* c, int64_t* step) {
 }
 
 int vaeb_clf_train_many(vaeb_clf* c, const int32_t* idx, int32_t n, int32_t batch, float* out) {
-    if (!c || !idx || !out || n <= 0 || batch <= 0) return fail(VAEB_ERR_ARG, "bad arguments");
-    if (batch > c->c.max_batch) return fail(VAEB_ERR_ARG, "batch %d > max_batch %d", batch, c->c.max_batch);
-    if (!c->x) return fail(VAEB_ERR_STATE, "vaeb_clf_set_data has not been called");
-    for (int i = 0; i < n; ++i)
-        if (idx[i] < 0 || idx[i] >= c->nrows)
-            return fail(VAEB_ERR_ARG, "row index %d out of range [0, %lld)", idx[i], (long long)c->nrows);
-    const int nb = cdiv(n, batch);
-    if (int rc = c->mem.grow(&c->idx, &c->idx_cap, n)) return rc;
-    if (int rc = c->mem.grow(&c->outs, &c->outs_cap, nb)) return rc;
-    HIP_TRY(hipMemcpyAsync(c->idx, idx, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->s));
-    for (int j = 0; j < nb; ++j) {
-        const int lb = j * batch, m = std::min(batch, n - lb);
-        if (int rc = clf_step(c, c->idx + lb, m, j)) return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(out, c->outs, sizeof(float) * (size_t)nb, hipMemcpyDeviceToHost, c->s));
-    HIP_TRY(hipStreamSynchronize(c->s));
-    return 0;
+    if (!c) return fail(VAEB_ERR_ARG, "bad arguments");
+    return core_train_many(c, c->x, c->nrows, "vaeb_clf_set_data", idx, n, batch, out, [] { return 0; },
+                           [c](const int* rows, int m, int slot, int64_t, int64_t) { return clf_step(c, rows, m, slot); });
 }
 
 int vaeb_clf_train(vaeb_clf* c, const int32_t* idx, int32_t n, float* out) {
@@ -393,14 +280,7 @@ int vaeb_clf_loglik(vaeb_clf* c, const float* x, const float* y, int64_t n, int3
         if (int rc = clf_eval_weights(c, draw, &th)) return rc;
         if (int rc = clf_forward(c, th, AeRows{c->xin, rows, nullptr}, rows)) return rc;
         if (int rc = clf_softmax(c, rows, AeRows{c->yin, rows, nullptr}, nullptr, nullptr)) return rc;
-        HIP_TRY(hipMemsetAsync(c->esum, 0, sizeof(double), c->s));
-        hipLaunchKernelGGL(iw_sum_kernel, dim3(1), dim3(256), 0, c->s, c->rowval, (int64_t)rows, c->esum);
-        CHECK_LAUNCH();
-        double part = 0.0;
-        HIP_TRY(hipMemcpyAsync(&part, c->esum, sizeof(double), hipMemcpyDeviceToHost, c->s));
-        HIP_TRY(hipStreamSynchronize(c->s));
-        total += part;
-        return 0;
+        return core_sum_to_host(c, c->rowval, rows, &total);
     });
     if (rc) return rc;
     *out_sum = total;

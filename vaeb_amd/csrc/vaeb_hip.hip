@@ -7,10 +7,11 @@
 // block (batch order, cursor, Philox step, ELBO accumulators) so a step needs no host
 // round trip and can be replayed as a hipGraph.
 //
-// Call map of the host layer (the engines' own maps: engine_f32.inc, engine_bf16.inc, engine_ae.inc):
+// Call map of the host layer (the engines' own maps: engine_f32.inc, engine_bf16.inc, stack_core.inc with
+// engine_ae.inc and engine_clf.inc):
 //   memory      every device buffer is allocated through a DevOwner (dev_owner.hpp) -- vaeb_ctx::mem,
-//               BfState::mem, vaeb_ae::mem -- and freed by its release_all (vaeb_destroy, bf_free,
-//               vaeb_ae_destroy); replaced buffers (data, xval, eps_in, bf.x | xbits | xval) go through
+//               BfState::mem, StackCore::mem -- and freed by its release_all (vaeb_destroy, bf_free,
+//               core_close); replaced buffers (data, xval, eps_in, bf.x | xbits | xval) go through
 //               drop / replace / grow, a call's scratch through a DevScratch guard.  No hipFree elsewhere.
 //   training    vaeb_update -> step_eager;  vaeb_update_many -> [eager first step + order_hook] run_steps
 //               (graph replay, or eager) -> enqueue_train_step -> the context's engine.  reset_graphs
@@ -1722,6 +1723,8 @@ int vaeb_kernel_name(int32_t id, char* out, int32_t cap) {
 
 }  // extern "C"
 
-// degenerate-vae autoencoder (vaeb_ae_*) on the same fp32 tile engine
+// the layer-stack engine on the same fp32 tile engine: the host core of its handles, then the
+// degenerate-vae autoencoder (vaeb_ae_*) and the softmax MLP classifier (vaeb_clf_*)
+#include "stack_core.inc"
 #include "engine_ae.inc"
 #include "engine_clf.inc"
